@@ -10,6 +10,10 @@ regions in flight on its GPU, no exchange while regions run, one gather of the F
 
 `python bench.py --gpus N` starts the N ranks itself (children are spawned before anything touches a GPU, the parent
 only relays rank 0's line); under `torch.distributed.run` the ranks come from the environment.  Prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, `--warmup` steps, `--steps` timed steps, the result line.  The
+other legs (the steps again with the ingest inside the clock, CPU baseline, the 100-region set, the saturation curve, the
+scaling model, stage 1) run with `--full`.  `--dump-outputs DIR` writes what the last timed step handed its caller.
 """
 import argparse
 import json
@@ -133,6 +137,23 @@ def depth_scan_leg(device, bases=100_000_000, depth=20.0, reps=3):
             "hbm_bytes": hbm, "hbm_GBps": hbm / (best[0] * 1e-3) / 1e9, "upload_ms": best[1], "host_prepare_ms": best[5],
             "intervals": best[4], "depth_sums_add_up": ok,
             "note": "the per-base array never reaches HBM: the rate against round 2's byte count can exceed what streaming that array allowed"}
+
+
+DUMP_SAMPLE = 4 << 20         # bytes of FASTA kept by --dump-outputs: 16 MB of float32 codes + 32 MB of float64 offsets
+
+
+def dump_outputs(dirname, fasta_text):
+    """--dump-outputs: the FASTA text the last timed step returned (all contigs of its region(s), in order) as the float32
+    codes of its bytes, DIR/fasta_bytes.npy.  A longer text is cut to a fixed, seeded sample of DUMP_SAMPLE bytes, whose
+    offsets go to DIR/fasta_bytes_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    codes = np.frombuffer((fasta_text or "").encode(), dtype=np.uint8).astype(np.float32)
+    if codes.size > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(codes.size, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(dirname, "fasta_bytes_index.npy"), idx.astype(np.float64))
+        codes = codes[idx]
+    np.save(os.path.join(dirname, "fasta_bytes.npy"), codes)
 
 
 def spawn_ranks(a):
@@ -291,6 +312,9 @@ def main():
     ap.add_argument("--sat-rounds", type=int, default=8, help="regions per slot of a saturation point: the ramp at the start and the drain at the "
                     "end weigh 1 / rounds (3 rounds: 1.76-1.81 M reads/s at 224 in flight; 8: 2.0 M, 12: 2.0 M)")
     ap.add_argument("--sat-distinct", type=int, default=32, help="distinct data sets of the saturation leg (reused cyclically)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (ingest inside the clock, CPU "
+                    "baseline, 100-region set, saturation, scaling model, stage 1); the --no-* options thin that out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -379,7 +403,7 @@ def main():
         # the slowest region of the set, alone on a GPU: the floor of the set's makespan however many GPUs share it
         # (rank 0 holds it: the longest-processing-time-first partition deals the costliest region first)
         slowest_alone = 0.0
-        if prepared:
+        if a.full and prepared:
             big = max(range(len(prepared)), key=lambda i: sum(sum(r.copies) for _, r in prepared[i][1]) if not isinstance(prepared[i], stage5.RegionFailure) else 0)
             stage5.run_regions(ctx, [prepared[big]], 1)
             t1 = time.time()
@@ -396,13 +420,15 @@ def main():
             all_stats += st
         fence()
         dt = max_over_ranks(time.time() - t0)
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, fasta_out)
         ingest_max = max_over_ranks(ingest_s)
         ctx.close()
         work = sum_over_ranks(sum(s["level_kernel_ticks"] for s in all_stats) / 1e5 / 1e3 / a.steps)
         # ---- ... and the same generator at a size that saturates every GPU (weak scaling): slots x rounds regions of the
         # configs[1] shape per rank, seeds continued from rank to rank
         sat = None
-        if not a.no_saturation:
+        if a.full and not a.no_saturation:
             ds = os.path.join(d, "sat%d" % rank)
             os.makedirs(ds, exist_ok=True)
             base = shape_regions(ds, a.sat_distinct, 1000 + rank * a.sat_distinct, a.reads, a.glen, a.strains)
@@ -470,20 +496,22 @@ def main():
         all_stats += st
     fence()
     dt = time.time() - t0
-    # the same steps with rows a1-a4 inside the clock: open + index the SAM, scan windows, view / crop / thin / dedup
-    fence()
-    t0 = time.time()
-    for _ in range(a.steps):
-        pa_i = cli.parse_cmd_line(argv)
-        with_ingest, _ = step([(pa_i, cli.load_regions(pa_i))])
-    fence()
-    dt_ingest = time.time() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, fasta_out)
+    if a.full:
+        # the same steps with rows a1-a4 inside the clock: open + index the SAM, scan windows, view / crop / thin / dedup
+        fence()
+        t0 = time.time()
+        for _ in range(a.steps):
+            pa_i = cli.parse_cmd_line(argv)
+            with_ingest, _ = step([(pa_i, cli.load_regions(pa_i))])
+        fence()
+        dt_ingest = time.time() - t0
     ctx.close()
     rl = roofline(all_stats, a.steps, 1)
 
     line = {"metric": "reads/sec into POA (150bp, ~1.5k-node graph)", "value": a.reads * a.steps / dt, "unit": "reads/s",
             "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
-            "ms_per_step_with_ingest": 1e3 * dt_ingest / a.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "configs[1]: %d x 150bp reads vs one %dbp gene, %d strains, seed 21, rambl.py options (%s)" % (
                 a.reads, a.glen, a.strains, RAMBL_OPTS),
@@ -491,9 +519,11 @@ def main():
                 "level_execution": single_mode, "input_reads": a.reads, "read_copies_after_ingest": n_graph},
             "roofline": rl,
             "breakdown_ms_per_step": breakdown(all_stats, a.steps),
-            "contigs": fasta_out.count(">") if fasta_out else 0,
-            "with_ingest_matches": with_ingest == fasta_out}
-    if not a.no_cpu:
+            "contigs": fasta_out.count(">") if fasta_out else 0}
+    if a.full:
+        line["ms_per_step_with_ingest"] = 1e3 * dt_ingest / a.steps
+        line["with_ingest_matches"] = with_ingest == fasta_out
+    if a.full and not a.no_cpu:
         cb, cargs = cpu_baseline(d, fasta, sam, "gene21:%s" % a.sample_roi)
         ref_fa = cb.pop("fasta")
         # the same sample on the GPU (ingest inside the clock, as the CPU figure has it): the like-for-like ratio
@@ -512,7 +542,7 @@ def main():
         cb["comparison"] = "the same sample on both sides, ingest included on both: gpu_same_sample_reads_per_s vs value (1 core) and vs all_cores.value"
         line["cpu_baseline"] = cb
     set_leg = None
-    if not a.no_set:
+    if a.full and not a.no_set:
         # the production shape (rambl.py stage 5 hands over one region per seed gene): the configs[2] set on this GPU with every
         # region in flight -- the N = 1 point of the sharded series that `--gpus N` runs; reported beside the headline, not as it
         ds = os.path.join(d, "set")
@@ -537,7 +567,7 @@ def main():
                    "cu_busy_frac": sum(s["level_kernel_ticks"] for s in st_set) / 1e5 / 1e3 / dts / N_CU,
                    "avg_sampler_level_ms": sum(s["chain_wall_ticks"] for s in st_set) / 1e5 / max(sum(s["sampler_launches"] for s in st_set), 1)}
         line["regions_in_flight"] = set_leg
-    if not a.no_saturation:
+    if a.full and not a.no_saturation:
         # how many regions in flight fill the GPU, and what it then sustains: regions of the headline's shape (configs[1]
         # generator, seeds 1000 ...), slots x rounds of them through a context with that many slots
         dsat = os.path.join(d, "sat")
@@ -554,7 +584,7 @@ def main():
             line["scaling_model"] = scaling_model(1, set_leg["work_level_kernel_seconds"], set_leg["slowest_region_alone_s"], best["busy_cus"], n_total)
             line["scaling_model"]["measured_makespan_s_one_gpu"] = set_leg["seconds"]
             line["scaling_model"]["workload"] = "the configs[2] set (what `--gpus N` shards): value = its alignments / predicted makespan"
-    if not a.no_depth:
+    if a.full and not a.no_depth:
         line["hbm_bound_kernel"] = depth_scan_leg(local)
     print(json.dumps(line), flush=True)
 

@@ -195,8 +195,13 @@ public:
     // a parked fiber may run again without a thread of its own watching for it (the completion stamps of the levels in
     // flight).  It returns whether anything is still being waited for: a spinning thread then keeps spinning instead of
     // going to sleep (nobody else would wake the parked fibers).  Set before any fiber is made ready; called from several
-    // threads at once.
-    void set_poll(std::function<bool()> poll) { poll_ = std::move(poll); if (max_spinners_ < 1) max_spinners_ = 1; }
+    // threads at once.  The executors are already running when it is set: they call it only once `polling_` says it is
+    // there (a std::function read while it is being assigned can be called through a null pointer).
+    void set_poll(std::function<bool()> poll) {
+        poll_ = std::move(poll);
+        if (max_spinners_ < 1) max_spinners_ = 1;
+        polling_.store(true, std::memory_order_release);
+    }
 
     // A fiber is about to park for something only the poll can see: somebody must be watching.  (Call after the thing to
     // watch has been published.)
@@ -230,6 +235,7 @@ private:
         sc_fiber_switch(&f->sp, *f->back);
         __builtin_trap();
     }
+    bool polling() const { return polling_.load(std::memory_order_acquire); }
     // The two queues are touched for a few nanoseconds at a time by the level server (a fiber per finished level) and by
     // every executor: a lock that never sleeps.  (They were under the mutex the executors also sleep on: eight executors
     // asking it for work at once put each other -- and the level server -- to sleep in the kernel, ~50 us per level at
@@ -265,7 +271,7 @@ private:
         if (on_start_) on_start_();
         void* self_sp = nullptr;
         for (;;) {
-            if (!lng && poll_) poll_();
+            if (!lng && polling()) poll_();
             Fiber* f = take(lng);
             if (!f) {
                 // Nothing ready (for this kind of thread).  A rank's CPU share is a quota of CPU TIME (a GPU box hands out 16
@@ -276,7 +282,7 @@ private:
                     spinners_.fetch_add(1, std::memory_order_acq_rel);
                     bool watch = false;
                     for (unsigned spins = 0; (spins < 6000 || watch) && !has_work(false) && !stop_.load(std::memory_order_relaxed); spins++) {
-                        if (poll_ && (spins & 7u) == 7u) watch = poll_();
+                        if ((spins & 7u) == 7u && polling()) watch = poll_();
                         __builtin_ia32_pause();
                     }
                     spinners_.fetch_sub(1, std::memory_order_acq_rel);
@@ -288,7 +294,7 @@ private:
                 // (with a poll: the last thread that could watch does not go to sleep while something is waited for)
                 if (stop_.load() && !has_work(lng)) { sl.fetch_sub(1, std::memory_order_seq_cst); return; }
                 holds_sleep_mu() = true;
-                const bool must_watch = !lng && poll_ && spinners_.load(std::memory_order_seq_cst) == 0 && poll_();
+                const bool must_watch = !lng && polling() && spinners_.load(std::memory_order_seq_cst) == 0 && poll_();
                 holds_sleep_mu() = false;
                 if (!has_work(lng) && !must_watch) {
                     (lng ? cv_long_ : cv_).wait_for(lk, std::chrono::milliseconds(lng ? 5 : 20));
@@ -317,6 +323,7 @@ private:
 
     std::function<void()> on_start_;
     std::function<bool()> poll_;
+    std::atomic<bool> polling_{false};
     std::vector<std::thread> threads_;
     std::mutex sleep_mu_;                        // the sleeping executors' (and all_'s); never held while a queue is touched
     std::condition_variable cv_, cv_long_;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-3 profiles (run on the GPU box from the repo root): rocprofv3 kernel statistics and the two PMC passes of
-#   bench    python3 bench.py --steps 2 --warmup 1 --no-cpu --no-set --no-saturation --no-depth   (configs[1], one region, a launch per level)
+#   bench    python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-set --no-saturation --no-depth   (configs[1], one region, a launch per level)
 #   set      SC_RESIDENT=0 python3 tools/inflight_probe.py 100                                      (100 regions in flight, a launch per level: per-level kernel spread)
 #   resident python3 tools/inflight_probe.py 224                                                    (224 regions in flight on resident workers: one dispatch per generation)
 #   depth    python3 tools/depth_bench.py 1e8 20 3                                                  (stage 1, k_depth_fused)
@@ -17,7 +17,7 @@ pass() {   # name, kind (stats | FETCH_SIZE | WRITE_SIZE), command...
     grep -h '^{' $out/${name}_$kind.log | tail -n 1 > $out/${name}_$kind.json
     echo "$name $kind ok"
 }
-B="python3 $repo/bench.py --no-cpu --no-set --no-saturation --no-depth"
+B="python3 $repo/bench.py --full --no-cpu --no-set --no-saturation --no-depth"
 pass bench stats $B --steps 2 --warmup 1 || exit 1
 pass bench FETCH_SIZE $B --steps 1 --warmup 0 || exit 1
 pass bench WRITE_SIZE $B --steps 1 --warmup 0 || exit 1
