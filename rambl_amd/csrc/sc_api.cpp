@@ -9,9 +9,9 @@
 // Polya-urn sampler -- is ONE kernel launch (k_level / k_level_sample), its parameters read from host-mapped memory,
 // its results and a completion stamp written back to it; the per-strain read log-likelihood rows never leave HBM.
 //
-// Per context: the level server (Ctx::serve_levels), the one thread that launches level kernels and watches the stamps.
-// Levels of different regions that need the same kernel leave as one grid on one of a few shared launch streams, so
-// that a hundred regions in flight need no more hardware queues than the GPU runs side by side.
+// Per context of several regions: resident level workers whose stamps the executor threads watch (Ctx::poll_stamps), or
+// with SC_RESIDENT=0 the level server (Ctx::serve_levels), which launches the levels of different regions as one grid on
+// one of a few shared streams, so that a hundred regions in flight need no more hardware queues than the GPU runs at once.
 #include <hip/hip_runtime.h>
 #include <malloc.h>
 
@@ -225,7 +225,6 @@ struct LevelRequest { Worker* w; LevelItem item; int kind; bool timed; };
 // that finds every stream busy waits in `pending` and leaves with the next batch of its kind.
 struct LaunchStream { hipStream_t st = nullptr; int busy = 0; int unretired = 0; };
 enum { GEN_STOPPED = 0, GEN_RUNNING = 1, GEN_STOPPING = 2 };
-constexpr int KIND_POSTED = -1;        // LevelRequest::kind of a level already in its slot's mailbox: the server only watches its stamp
 struct Ctx {
     int device = 0;
     // page-locked staging arenas, shared: a region holds one only while it is set up, so a handful serves any number in flight
@@ -264,7 +263,7 @@ struct Ctx {
     LevelParams* Pd_all = nullptr;
     std::vector<LaunchStream> lstreams;
     std::vector<hipStream_t> setup_streams;   // uploads, graph kernels: shared round-robin by the workers
-    // the level server: one thread launches every level and sees every completion stamp (serve_levels)
+    // the level server (SC_RESIDENT=0, several slots): one thread launches every level and sees every stamp (serve_levels)
     sc::SpinLock plk;                         // guards pending (a few nanoseconds per level from every executor: never a sleeping lock)
     std::deque<LevelRequest> pending;         // requests the server has not taken yet
     std::atomic<int> n_pending{0};
@@ -275,14 +274,13 @@ struct Ctx {
     std::thread server;
     void submit_level(const LevelRequest& rq);
     void serve_levels();
-    // Resident contexts without a level server (SC_POLL_EXEC, the default): a worker whose level is in its mailbox raises
-    // its flag and parks; the continuation threads look at the flagged workers' stamps between two fibers and while they
-    // spin for one (FiberPool::set_poll), and the thread that sees a stamp makes the region ready.  The CPU the server spent
+    // Resident contexts of several regions have no level server: a worker whose level is in its mailbox arms its slot of
+    // `watch` and parks; the continuation threads look at the armed slots' stamps between two fibers and while they spin
+    // for one (FiberPool::set_poll), and the thread that sees a stamp makes the region ready.  The CPU a server would spend
     // going round the stamps is an executor's.
-    bool poll_exec = false;
-    std::unique_ptr<std::atomic<uint8_t>[]> polled;      // [workers]: 1 = parked until its level's stamp arrives
+    std::unique_ptr<StampWatch> watch;                   // [workers]; null in other contexts
     bool poll_stamps();                                  // true: some worker is still waiting for its stamp
-    void poll_health();                                  // the heart thread, once a second: flagged workers whose workgroup has gone
+    void poll_health();                                  // the heart thread, once a second: armed workers whose workgroup has gone
     double* dU = nullptr;             // uniform stream on the device
     float* dUf = nullptr;             // fp32 copy
     // Resident level workers (k_level_resident): while regions are in flight one workgroup per slot stays on its CU and
@@ -309,7 +307,7 @@ struct Ctx {
     long generations = 0;
     std::thread heart;                // keeps ResidentCtl::heartbeat moving while the context lives
     std::atomic<bool> heart_stop{false};
-    void resident_ensure(Worker* w);
+    void resident_ensure(int m);
     void resident_idle();
     void resident_shutdown();
 };
@@ -408,14 +406,13 @@ struct Worker {
     hipStream_t st = nullptr;         // a setup stream of the context (not owned), or a private one (own_stream)
     bool own_stream = false;
     hipEvent_t sync_ev = nullptr;     // marks "everything this worker has put on `st` so far" (sync_stream)
-    // hand-shake with the level server: 1 = a level is on its way / in flight, 2 = its stamp was seen, 3 = failed
+    // hand-shake with whoever sees the level's stamp: 1 = a level is on its way / in flight, 2 = its stamp was seen, 3 = failed
     std::atomic<int> level_state{0};
-    unsigned level_want = 0;          // stamp of that level
     int cur_stream = -1;              // its launch stream (server's bookkeeping)
     std::string level_err;
     double t_seen = 0, wake_acc[2] = {0, 0};
-    int mslot = -1;                   // the mailbox (= workgroup of the resident grid) this region walks on, -1 while it has none
-    double t_posted = 0;              // when the level went into the slot's mailbox (resident workers)
+    std::atomic<int> mslot{-1};       // the mailbox (= workgroup of the resident grid) this region walks on, -1 while it has none
+    std::atomic<double> t_posted{0};  // when the level was handed over (the heart thread judges resident workgroups by it)
     double t_batch_launched = 0;      // diagnostics: when the level's batch was launched, and its size
     int batch_n = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;     // the pair of the level being launched (from ev_pool when timing)
@@ -427,7 +424,7 @@ struct Worker {
     LevelResult* Rh = nullptr;        // host-mapped, written by the kernel, stamped last
     LevelResult* Rd = nullptr;
     bool own_blocks = false;          // Ph / Pd / Rh are this worker's own allocations (sc_msa_align's private worker)
-    unsigned seq = 0;                 // stamp of the last level launched
+    unsigned seq = 0;                 // stamp of the last level launched (the level server waits for it)
     DevBuf b_ent_rid, b_ent_cn, b_ent_lab_off, b_ent_lab_len, b_ent_first, b_ent_qoff, b_labels, b_mate_ptr, b_mate_idx,
         b_ll, b_has, b_isnew, b_tabA, b_tabLf, b_qcode, b_qent, b_quid, b_out_ptr, b_out_node, b_pool_ptr, b_pool_rid,
         b_pool_cn, b_isend, b_esrc, b_support, b_jobdev;
@@ -444,7 +441,9 @@ struct Worker {
     void init();
     void run();
     void process(Job& job);
+    void complete_level(const LevelItem& it, bool timed);
     void wait_level();
+    void finish_level(int state, const char* err = nullptr);
     void sync_stream();
     int msa_device(const std::vector<std::string>& seqs, std::vector<std::string>& rows);
     void thread_device(const std::string& G, const std::vector<AlignedRead>& R, const std::vector<std::vector<CigarOp>>& cig,
@@ -488,16 +487,16 @@ void Worker::sync_stream() {
     }
 }
 
-// The level server.  Workers hand their next level to this thread and park; it is the only thread that launches level
-// kernels and the only one that watches the completion stamps, so a finished level is seen within a microsecond
-// however many regions are in flight, and nobody polls or contends for the launch path.
+// The level server (SC_RESIDENT=0, several slots).  Workers hand their next level to this thread and park; it is the only
+// thread that launches level kernels and the only one that watches the completion stamps, so a finished level is seen
+// within a microsecond however many regions are in flight, and nobody polls or contends for the launch path.
 //   * A level's kernel stores its stamp into host memory after everything else it reports (system-scope release):
 //     completion is seen without a stream synchronisation; the region's fiber is made ready and an executor thread
 //     picks it up (no futex round trip per level).
 //   * Launch streams are shared by all regions.  A stream carries one batch at a time, so kernels of different
 //     regions never queue behind each other; while a stream is free, every waiting level (up to MAXB) leaves as one
 //     grid, workgroup b = region b of the batch: the kernel of their kind when they all need the same one, k_level_any
-//     (which calls the variant each item names) otherwise.  SC_ANY_KIND=0 keeps one kind per launch (measurements).
+//     (which calls the variant each item names) otherwise.
 //   * A launch the runtime rejects fails the levels of its batch at once; a stream that drains while stamps of its
 //     batch are still missing (a kernel that ended without stamping) fails them at the periodic check.
 PinnedArena* Ctx::lease_arena(PinnedArena* passthrough) {
@@ -521,44 +520,16 @@ void Ctx::serve_levels() {
     std::deque<LevelRequest> waiting;          // taken from `pending`, not launched yet
     std::vector<Worker*> flying;               // launched, stamp not seen yet
     std::string dead;                          // non-empty: a launch stream has failed, every level fails from now on
-    auto finish = [this](Worker* w, int state, const std::string& err) {
-        w->level_err = err;
-        w->t_seen = now_ms();
-        w->level_state.store(state, std::memory_order_release);
-        pool->make_ready(w->fib);
-    };
-    auto stamped = [](Worker* w) { return __atomic_load_n(&w->Rh->seq, __ATOMIC_ACQUIRE) == w->level_want; };
-    // a resident workgroup that has left (heartbeat limit, or a fault that ended the grid) or never started will not stamp
-    auto check_resident = [&]() {
-        if (!resident) return;
-        for (size_t i = 0; i < flying.size();) {
-            Worker* w = flying[i];
-            if (w->mslot < 0) { ++i; continue; }
-            const unsigned ms = __atomic_load_n(&mail_h[w->mslot].state, __ATOMIC_ACQUIRE);
-            const bool never = ms == 0u && now_ms() - w->t_posted > 20000.0;       // more slots than the GPU holds resident
-            if (w->cur_stream >= 0 || (ms < 2u && !never) || stamped(w)) { ++i; continue; }
-            flying[i] = flying.back(); flying.pop_back();
-            finish(w, 3, never ? "the slot's resident level worker has not started within 20 s (more slots than the GPU holds resident workgroups?)"
-                         : ms == 3u ? "the slot's resident level worker received an item that was not its own"
-                                    : "the slot's resident level worker has left before the level was done");
-        }
-    };
-    unsigned loops = 0;
+    auto stamped = [](Worker* w) { return __atomic_load_n(&w->Rh->seq, __ATOMIC_ACQUIRE) == w->seq; };
     unsigned idle_spins = 0;
-    double t_check = now_ms();
     const bool sweep_log = getenv("SC_SERVER_LOG") != nullptr;          // diagnostics: how long one round of the loop takes while levels fly
     double sweep_t0 = 0, sweep_sum = 0, sweep_max = 0; long sweep_n = 0, sweep_fly = 0;
-    const bool any_kind = !(getenv("SC_ANY_KIND") && atoi(getenv("SC_ANY_KIND")) == 0);
     for (;;) {
         if (n_pending.load(std::memory_order_seq_cst) > 0) {
-            int took = 0;
             plk.lock();
-            while (!pending.empty()) {
-                if (pending.front().kind == KIND_POSTED) { pending.front().w->cur_stream = -1; flying.push_back(pending.front().w); }
-                else waiting.push_back(pending.front());
-                pending.pop_front();
-                took++;
-            }
+            const int took = (int)pending.size();
+            waiting.insert(waiting.end(), pending.begin(), pending.end());
+            pending.clear();
             plk.unlock();
             n_pending.fetch_sub(took, std::memory_order_seq_cst);
         } else if (waiting.empty() && flying.empty()) {
@@ -571,7 +542,6 @@ void Ctx::serve_levels() {
             if (server_stop.load(std::memory_order_seq_cst)) break;
             continue;
         }
-        if ((++loops & 0xFFFFu) == 0 && resident && now_ms() - t_check > 2000.0) { t_check = now_ms(); check_resident(); }
         bool progressed = false;
         if (sweep_log) {
             const double t = now_ms();
@@ -582,10 +552,9 @@ void Ctx::serve_levels() {
         for (size_t i = 0; i < flying.size();) {
             Worker* w = flying[i];
             if (stamped(w)) {
-                if (w->cur_stream >= 0) lstreams[(size_t)w->cur_stream].busy--;
-                w->cur_stream = -1;
+                lstreams[(size_t)w->cur_stream].busy--;
                 flying[i] = flying.back(); flying.pop_back();
-                finish(w, 2, "");
+                w->finish_level(2);
                 progressed = true;
             } else {
                 ++i;
@@ -593,7 +562,7 @@ void Ctx::serve_levels() {
         }
         // launches
         while (!waiting.empty()) {
-            if (!dead.empty()) { finish(waiting.front().w, 3, dead); waiting.pop_front(); progressed = true; continue; }
+            if (!dead.empty()) { waiting.front().w->finish_level(3, dead.c_str()); waiting.pop_front(); progressed = true; continue; }
             int fs = -1;
             for (size_t i = 0; i < lstreams.size(); i++) if (lstreams[i].busy == 0) { fs = (int)i; break; }
             if (fs < 0) break;
@@ -603,7 +572,7 @@ void Ctx::serve_levels() {
             int n = 0;
             bool timed = false, mixed = false;
             for (auto it = waiting.begin(); it != waiting.end() && n < MAXB;) {
-                if (it->kind != kind) { if (!any_kind) { ++it; continue; } mixed = true; }
+                mixed = mixed || it->kind != kind;
                 batch.it[n] = it->item;
                 who[n++] = it->w;
                 timed = timed || it->timed;
@@ -618,7 +587,7 @@ void Ctx::serve_levels() {
             if (le != hipSuccess) {
                 // the runtime did not take the launch: nothing of this batch will ever stamp
                 const std::string msg = std::string("level kernel launch: ") + hipGetErrorString(le);
-                for (int i = 0; i < n; i++) finish(who[i], 3, msg);
+                for (int i = 0; i < n; i++) who[i]->finish_level(3, msg.c_str());
                 progressed = true;
                 continue;
             }
@@ -651,22 +620,20 @@ void Ctx::serve_levels() {
                     Worker* w = flying[i];
                     if (w->cur_stream != (int)si || stamped(w)) { ++i; continue; }
                     ls.busy--;
-                    w->cur_stream = -1;
                     flying[i] = flying.back(); flying.pop_back();
-                    finish(w, 3, "a level kernel ended without its completion stamp");
+                    w->finish_level(3, "a level kernel ended without its completion stamp");
                 }
             }
-            check_resident();
             if (!dead.empty()) {
-                for (Worker* w : flying) { if (w->cur_stream >= 0) lstreams[(size_t)w->cur_stream].busy = 0; w->cur_stream = -1; finish(w, 3, dead); }
+                for (Worker* w : flying) { lstreams[(size_t)w->cur_stream].busy = 0; w->finish_level(3, dead.c_str()); }
                 flying.clear();
             }
         }
     }
     if (sweep_log && sweep_n) fprintf(stderr, "level server: %ld rounds with levels flying, %.2f us each (longest %.1f us), %.1f levels flying on average\n",
                                       sweep_n, 1e3 * sweep_sum / sweep_n, 1e3 * sweep_max, (double)sweep_fly / sweep_n);
-    for (Worker* w : flying) finish(w, 3, "context destroyed");
-    for (auto& rq : waiting) finish(rq.w, 3, "context destroyed");
+    for (Worker* w : flying) w->finish_level(3, "context destroyed");
+    for (auto& rq : waiting) rq.w->finish_level(3, "context destroyed");
 }
 void Ctx::setup_enter(Worker* w) {
     {
@@ -690,32 +657,32 @@ int Ctx::acquire_mailbox(Worker* w) {
     {
         std::lock_guard<std::mutex> lk(mmu);
         if (!free_mail.empty()) { const int m = free_mail.back(); free_mail.pop_back(); return m; }
-        w->mslot = -1;
+        w->mslot.store(-1, std::memory_order_release);
         mail_waiters.push_back(w);
     }
     FiberPool::park();                         // release_mailbox hands one over (w->mslot) and makes the fiber ready
-    return w->mslot;
+    return w->mslot.load(std::memory_order_acquire);
 }
 void Ctx::release_mailbox(int m) {
     Worker* next = nullptr;
     {
         std::lock_guard<std::mutex> lk(mmu);
-        if (!mail_waiters.empty()) { next = mail_waiters.front(); mail_waiters.pop_front(); next->mslot = m; }
+        if (!mail_waiters.empty()) { next = mail_waiters.front(); mail_waiters.pop_front(); next->mslot.store(m, std::memory_order_release); }
         else free_mail.push_back(m);
     }
     if (next) pool->make_ready(next->fib);
 }
-// A level is about to be posted to slot w->slot: make sure a generation of the resident grid is there to take it.
-void Ctx::resident_ensure(Worker* w) {
+// A level is about to be posted to mailbox m: make sure a generation of the resident grid is there to take it.
+void Ctx::resident_ensure(int m) {
     // the ordinary case, once per level from every executor, takes no lock: the generation runs and the mailbox's workgroup is there
-    if (gen_state.load(std::memory_order_acquire) == GEN_RUNNING && __atomic_load_n(&mail_h[w->mslot].state, __ATOMIC_ACQUIRE) < 2u) return;
+    if (gen_state.load(std::memory_order_acquire) == GEN_RUNNING && __atomic_load_n(&mail_h[m].state, __ATOMIC_ACQUIRE) < 2u) return;
     const double t0 = now_ms();
     for (;;) {
         if (now_ms() - t0 > 60000.0) throw HipError("resident level workers: the previous grid has not left after a minute");
         {
             std::lock_guard<std::mutex> lk(gen_mu);
             if (gen_state == GEN_RUNNING) {
-                if (__atomic_load_n(&mail_h[w->mslot].state, __ATOMIC_ACQUIRE) < 2u) return;
+                if (__atomic_load_n(&mail_h[m].state, __ATOMIC_ACQUIRE) < 2u) return;
                 // the slot's workgroup has left although regions are in flight (the heartbeat limit): end this generation
                 __atomic_store_n(&ctl_h->stop, 1u, __ATOMIC_RELEASE);
                 gen_state = GEN_STOPPING;
@@ -766,57 +733,27 @@ void Ctx::resident_shutdown() {
     }
     gen_state = GEN_STOPPED;
 }
+// Why a level posted to resident workgroup `mb` will never be stamped `want`, or nullptr while it still may be.  (The
+// mailbox's state is read before the stamp: a workgroup stamps its last level before it leaves.)
+static const char* resident_failure(const Mailbox& mb, const unsigned* stamp, unsigned want, double t_posted) {
+    const unsigned ms = __atomic_load_n(&mb.state, __ATOMIC_ACQUIRE);
+    const bool never = ms == 0u && now_ms() - t_posted > 20000.0;       // more slots than the GPU holds resident
+    if ((ms < 2u && !never) || __atomic_load_n(stamp, __ATOMIC_ACQUIRE) == want) return nullptr;
+    return never ? "the slot's resident level worker has not started within 20 s (more slots than the GPU holds resident workgroups?)"
+         : ms == 3u ? "the slot's resident level worker received an item that was not its own"
+                    : "the slot's resident level worker has left before the level was done";
+}
 bool Ctx::poll_stamps() {
-    const size_t n = workers.size();
-    bool waiting = false;
-    for (size_t i = 0; i < n; i++) {
-        if (polled[i].load(std::memory_order_acquire) != 1) continue;
-        Worker* w = workers[i].get();
-        if (__atomic_load_n(&w->Rh->seq, __ATOMIC_ACQUIRE) != w->level_want) { waiting = true; continue; }
-        uint8_t one = 1;
-        if (!polled[i].compare_exchange_strong(one, 0, std::memory_order_acq_rel)) continue;      // another thread saw it first
-        // The flag is this thread's now -- but is it still the flag of the level whose stamp was seen?  Another thread may
-        // have seen that stamp first, the region may have run on and be parked for its NEXT level by the time the exchange
-        // above succeeded (it then took the new level's flag).  Look again, with the flag in hand: nothing changes under it.
-        if (__atomic_load_n(&w->Rh->seq, __ATOMIC_ACQUIRE) != w->level_want) {
-            polled[i].store(1, std::memory_order_seq_cst);
-            waiting = true;
-            continue;
-        }
-        w->t_seen = now_ms();
-        w->level_state.store(2, std::memory_order_release);
-        pool->make_ready(w->fib);
-    }
-    return waiting;
+    return watch->poll([this](size_t i) { return &workers[i]->Rh->seq; }, [this](size_t i) { workers[i]->finish_level(2); });
 }
 void Ctx::poll_health() {
-    const size_t n = workers.size();
-    for (size_t i = 0; i < n; i++) {
-        if (polled[i].load(std::memory_order_acquire) != 1) continue;
-        Worker* w = workers[i].get();
-        const int m = w->mslot;
-        if (m < 0) continue;
-        const unsigned ms = __atomic_load_n(&mail_h[m].state, __ATOMIC_ACQUIRE);
-        const bool never = ms == 0u && now_ms() - w->t_posted > 20000.0;       // more slots than the GPU holds resident
-        if ((ms < 2u && !never) || __atomic_load_n(&w->Rh->seq, __ATOMIC_ACQUIRE) == w->level_want) continue;
-        uint8_t one = 1;
-        if (!polled[i].compare_exchange_strong(one, 0, std::memory_order_acq_rel)) continue;
-        {   // (as in poll_stamps: with the flag in hand, is it still the level that was judged?)
-            const int m2 = w->mslot;
-            const unsigned ms2 = m2 >= 0 ? __atomic_load_n(&mail_h[m2].state, __ATOMIC_ACQUIRE) : 0u;
-            const bool never2 = ms2 == 0u && now_ms() - w->t_posted > 20000.0;
-            if (m2 != m || (ms2 < 2u && !never2) || __atomic_load_n(&w->Rh->seq, __ATOMIC_ACQUIRE) == w->level_want) {
-                polled[i].store(1, std::memory_order_seq_cst);
-                continue;
-            }
-        }
-        w->level_err = never ? "the slot's resident level worker has not started within 20 s (more slots than the GPU holds resident workgroups?)"
-                     : ms == 3u ? "the slot's resident level worker received an item that was not its own"
-                                : "the slot's resident level worker has left before the level was done";
-        w->t_seen = now_ms();
-        w->level_state.store(3, std::memory_order_release);
-        pool->make_ready(w->fib);
-    }
+    watch->check(
+        [this](size_t i, unsigned want) -> const char* {
+            const Worker* w = workers[i].get();
+            const int m = w->mslot.load(std::memory_order_acquire);
+            return m < 0 ? nullptr : resident_failure(mail_h[m], &w->Rh->seq, want, w->t_posted.load(std::memory_order_acquire));
+        },
+        [this](size_t i, const char* why) { workers[i]->finish_level(3, why); });
 }
 void Ctx::submit_level(const LevelRequest& rq) {
     rq.w->level_state.store(1, std::memory_order_release);
@@ -829,19 +766,84 @@ void Ctx::submit_level(const LevelRequest& rq) {
         dcv.notify_one();
     }
 }
-// The region's fiber parks until the server has seen the level's stamp (or failed the level).  The server makes the
-// fiber ready exactly once per request, so the fiber parks exactly once per request -- also when the level is already
-// done by the time it gets here (it then comes straight back).
+// The region's fiber parks until the level server or an executor has seen the level's stamp (or failed the level).  That
+// thread makes the fiber ready exactly once per level (finish_level), so the fiber parks exactly once per level -- also
+// when the level is already done by the time it gets here (it then comes straight back).
 void Worker::wait_level() {
     const double t_park = now_ms();
     FiberPool::park();
     const double t_back = now_ms();
-    wake_acc[0] += t_park - t_posted;           // handing the level to the server
-    wake_acc[1] += t_back - t_seen;             // the server has seen the stamp -> this fiber runs again
+    wake_acc[0] += t_park - t_posted.load(std::memory_order_relaxed);      // handing the level over
+    wake_acc[1] += t_back - t_seen;             // the stamp has been seen -> this fiber runs again
     if (ctx->wake_hist) { const double us = 1e3 * (t_back - t_seen); int b = 0; while (b < 23 && us >= (double)(1 << b)) b++; ctx->wake_hist[b].fetch_add(1, std::memory_order_relaxed); }
     const int state = level_state.load(std::memory_order_acquire);
     if (state == 3) throw HipError(level_err);
     if (state != 2) throw HipError("a region was resumed before its level was done");
+}
+// The level's wait is over (2: its stamp was seen, 3: failed, `err` says why): the region's fiber may run.  Once per wait.
+void Worker::finish_level(int state, const char* err) {
+    if (err) level_err = err;
+    t_seen = now_ms();
+    level_state.store(state, std::memory_order_release);
+    ctx->pool->make_ready(fib);
+}
+// Hands a level to the GPU and returns once its completion stamp has been seen; throws when it never will be.  A resident
+// context posts the level to the region's mailbox, any other launches it: the worker itself when it is the context's
+// only one, the level server otherwise.  The only worker of a context spins for the stamp itself; any other parks until
+// the executors (resident) or the level server have seen it.
+void Worker::complete_level(const LevelItem& it, bool timed) {
+    const unsigned want = it.h.seq;
+    const bool alone = ctx->workers.size() == 1;
+    if (ctx->resident) {
+        // the slot's resident workgroup takes the level from its mailbox: the item, then its stamp (release)
+        const int m = mslot.load(std::memory_order_relaxed);
+        ctx->resident_ensure(m);
+        Mailbox& mb = ctx->mail_h[m];
+        mb.item = it;
+        __atomic_store_n(&mb.seq, want, __ATOMIC_RELEASE);
+        const double t = now_ms();
+        t_posted.store(t, std::memory_order_release);
+        t_batch_launched = t; batch_n = 1;
+        if (alone) {
+            for (unsigned spins = 0; __atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != want;) {
+                __builtin_ia32_pause();
+                if ((++spins & 0xFFFFFu) == 0)
+                    if (const char* why = resident_failure(mb, &Rh->seq, want, t)) throw HipError(why);
+            }
+        } else {
+            level_state.store(1, std::memory_order_release);
+            ctx->watch->arm((size_t)slot, want);        // (the mailbox and t_posted are written: an executor may look)
+            ctx->pool->ensure_poller();
+            wait_level();
+        }
+        __atomic_store_n(&ctx->mail_done[(size_t)m], want, __ATOMIC_RELEASE);
+    } else if (alone) {
+        // nobody to batch with: the worker launches its level itself
+        LevelBatch batch;
+        batch.it[0] = it;
+        hipStream_t ls = ctx->lstreams[0].st;
+        if (timed) HIPCHK(hipEventRecord(ev0, ls));
+        (void)hipGetLastError();
+        launch_level_batch(ls, it.kind & 0xFF, batch, 1);
+        { const hipError_t le = hipGetLastError(); if (le != hipSuccess) throw HipError(std::string("level kernel launch: ") + hipGetErrorString(le)); }
+        if (timed) HIPCHK(hipEventRecord(ev1, ls));
+        t_batch_launched = now_ms(); batch_n = 1;
+        // while this level runs: let the runtime retire the launches behind it (it does so only when asked, and a
+        // region leaves ~1 500 of them for whoever synchronises the device next: ~10 us each)
+        (void)hipStreamQuery(ls);
+        for (unsigned spins = 0; __atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != want;) {
+            __builtin_ia32_pause();
+            if ((++spins & 0x3FFFFu) == 0) {             // every few milliseconds: has the stream died?
+                const hipError_t e = hipStreamQuery(ls);
+                if (e == hipSuccess) { if (__atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != want) throw HipError("a level kernel ended without its completion stamp"); }
+                else if (e != hipErrorNotReady) throw HipError(std::string("level kernel: ") + hipGetErrorString(e));
+            }
+        }
+    } else {
+        t_posted.store(now_ms(), std::memory_order_release);
+        ctx->submit_level(LevelRequest{this, it, it.kind & 0xFF, timed});
+        wait_level();
+    }
 }
 
 // a7 on the device.  Returns the number of columns.
@@ -1152,12 +1154,12 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
     job.stats.setup_ms = now_ms() - t_cluster0;
     struct MailHold {                  // the mailbox the region walks on (resident workers): taken now, handed on when the walk ends
         Worker* w;
-        void drop() { if (w->mslot >= 0) { const int m = w->mslot; w->mslot = -1; w->ctx->release_mailbox(m); } }
+        void drop() { const int m = w->mslot.load(std::memory_order_relaxed); if (m >= 0) { w->mslot.store(-1, std::memory_order_release); w->ctx->release_mailbox(m); } }
         ~MailHold() { drop(); }
     } mail_hold{this};
     if (ctx->resident) {
         const double t_m0 = now_ms();
-        mslot = ctx->acquire_mailbox(this);
+        mslot.store(ctx->acquire_mailbox(this), std::memory_order_release);
         job.stats.mailbox_ms = now_ms() - t_m0;
         __atomic_store_n(&Rh->seq, 0u, __ATOMIC_RELEASE);       // (stamps are the mailbox's from here on: never 0)
     }
@@ -1307,8 +1309,8 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
             H.done = launch_level_grid(st, jd, H, Pd, Rd);
             sync_stream();                               // the level's kernel runs on another stream
         }
-        H.seq = (ctx->resident && mslot >= 0) ? ++ctx->mail_seq[(size_t)mslot] : ++seq;     // (a mailbox keeps its own count: regions take turns on it)
-        level_want = H.seq;
+        const int ms = mslot.load(std::memory_order_relaxed);
+        H.seq = ms >= 0 ? ++ctx->mail_seq[(size_t)ms] : ++seq;     // (a mailbox keeps its own count: regions take turns on it)
         if (timed) {
             // a fresh pair of events per sampler launch; their times are read after the walk, not between levels
             if (ev_used + 2 > ev_pool.size()) {
@@ -1321,63 +1323,8 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
         }
         const double t_launched = level_log ? now_ms() : 0.0;
         lap(0);
-        if (ctx->resident) {
-            // the slot's resident workgroup takes the level from its mailbox: the item, then its stamp (release)
-            ctx->resident_ensure(this);
-            Mailbox& mb = ctx->mail_h[mslot];
-            mb.item = LevelItem{jd_dev, H, level_kind(H) | (level_lds_kb(H, K) << 8), Pm, Rd};
-            __atomic_store_n(&mb.seq, H.seq, __ATOMIC_RELEASE);
-            t_posted = now_ms();
-            t_batch_launched = level_log ? t_posted : 0.0; batch_n = 1;
-            if (ctx->workers.size() == 1) {
-                unsigned spins = 0;
-                while (__atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != H.seq) {
-                    __builtin_ia32_pause();
-                    if ((++spins & 0xFFFFFu) != 0) continue;
-                    const unsigned ms = __atomic_load_n(&mb.state, __ATOMIC_ACQUIRE);
-                    if (ms >= 2u && __atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != H.seq)
-                        throw HipError("the resident level worker has left before the level was done");
-                    if (ms == 0u && now_ms() - t_posted > 20000.0) throw HipError("the resident level worker has not started within 20 s");
-                }
-            } else {
-                if (ctx->poll_exec) {
-                    level_state.store(1, std::memory_order_release);
-                    ctx->polled[(size_t)slot].store(1, std::memory_order_seq_cst);      // (level_want and the mailbox are written: an executor may look)
-                    ctx->pool->ensure_poller();
-                } else {
-                    ctx->submit_level(LevelRequest{this, LevelItem{}, KIND_POSTED, false});
-                }
-                wait_level();
-            }
-        } else if (ctx->workers.size() == 1) {
-            // a single region in flight: nobody to batch with, so the worker launches its level itself and watches the stamp
-            LevelBatch batch;
-            batch.it[0] = LevelItem{jd_dev, H, level_kind(H) | (level_lds_kb(H, K) << 8), Pm, Rd};
-            hipStream_t ls = ctx->lstreams[0].st;
-            if (timed) HIPCHK(hipEventRecord(ev0, ls));
-            (void)hipGetLastError();
-            launch_level_batch(ls, level_kind(H), batch, 1);
-            { const hipError_t le = hipGetLastError(); if (le != hipSuccess) throw HipError(std::string("level kernel launch: ") + hipGetErrorString(le)); }
-            if (timed) HIPCHK(hipEventRecord(ev1, ls));
-            t_batch_launched = level_log ? now_ms() : 0.0; batch_n = 1;
-            // while this level runs: let the runtime retire the launches behind it (it does so only when asked, and a
-            // region leaves ~1 500 of them for whoever synchronises the device next: ~10 us each)
-            (void)hipStreamQuery(ls);
-            unsigned spins = 0;
-            while (__atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != H.seq) {
-                __builtin_ia32_pause();
-                if ((++spins & 0x3FFFFu) == 0) {             // every few milliseconds: has the stream died?
-                    const hipError_t e = hipStreamQuery(ls);
-                    if (e == hipSuccess) { if (__atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != H.seq) throw HipError("a level kernel ended without its completion stamp"); }
-                    else if (e != hipErrorNotReady) throw HipError(std::string("level kernel: ") + hipGetErrorString(e));
-                }
-            }
-        } else {
-            t_posted = now_ms();
-            ctx->submit_level(LevelRequest{this, LevelItem{jd_dev, H, level_kind(H) | (level_lds_kb(H, K) << 8), Pm, Rd}, level_kind(H), timed});
-            wait_level();
-        }
-        if (ctx->resident && mslot >= 0) __atomic_store_n(&ctx->mail_done[(size_t)mslot], H.seq, __ATOMIC_RELEASE);
+        const int kind = level_kind(H);
+        complete_level(LevelItem{jd_dev, H, kind | (level_lds_kb(H, K) << 8), Pm, Rd}, timed);
         t_mark = now_ms();                                   // (the wait for the level is not host work)
         level_launches++;
         if (chain) {
@@ -1398,7 +1345,7 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
             t_last_done = t_done;
         }
         job.stats.xcd_levels[Rh->xcc & 7]++;
-        job.stats.kind_levels[std::min(std::max(level_kind(H), 0), 16)]++;
+        job.stats.kind_levels[std::min(std::max(kind, 0), 16)]++;
     };
 
     struct Cand { int parent; int node; ld abundance; };
@@ -1881,13 +1828,10 @@ int sc_ctx_create(int device, int stream_count, sc_ctx** out) {
     }
     int plan[3] = {1, 0, 1};
     (void)sc_host_plan(stream_count, 0, 0.0, plan);
-    {
-        // resident contexts of several regions: the executors watch the stamps themselves, and the level server's CPU is one more
-        // executor's (SC_POLL_EXEC=0: the level server as for a launch per level)
-        const char* pe = getenv("SC_POLL_EXEC");
-        ctx->poll_exec = ctx->resident && stream_count > 1 && !(pe && atoi(pe) == 0);
-        if (ctx->poll_exec && plan[1] > 0) plan[0] = std::min(plan[0] + 1, std::min(stream_count, 32));
-    }
+    // resident contexts of several regions: the executors watch the stamps themselves, and the level server's CPU is one more
+    // executor's
+    const bool watch = ctx->resident && stream_count > 1;
+    if (watch && plan[1] > 0) plan[0] = std::min(plan[0] + 1, std::min(stream_count, 32));
     if (const char* e = getenv("SC_EXEC_THREADS")) { const int k = atoi(e); if (k >= 1) plan[0] = std::min(k, stream_count); }
     {
         // page-locked staging of the regions' transfers: only worth it while other regions are in flight (it is their queues
@@ -1934,14 +1878,6 @@ int sc_ctx_create(int device, int stream_count, sc_ctx** out) {
         }
         std::memset(ctx->mail_h, 0, nm * sizeof(Mailbox));
         std::memset(ctx->ctl_h, 0, sizeof(ResidentCtl));
-        ctx->heart = std::thread([ctx] {
-            unsigned beats = 0;
-            while (!ctx->heart_stop.load(std::memory_order_acquire)) {
-                __atomic_fetch_add(&ctx->ctl_h->heartbeat, 1u, __ATOMIC_RELEASE);
-                if (ctx->poll_exec && ctx->pool && (++beats % 50u) == 0) ctx->poll_health();
-                std::this_thread::sleep_for(std::chrono::milliseconds(20));
-            }
-        });
     }
     const int dev = device;
     // half of the executor threads take the regions' set-ups first (graph construction: tens of milliseconds each), the other
@@ -1952,12 +1888,21 @@ int sc_ctx_create(int device, int stream_count, sc_ctx** out) {
     if (!getenv("SC_SETUP_LIMIT") && n_long > 0) ctx->setup_limit = 2 * n_long;      // a set-up waits for the GPU part of its time
     ctx->pool.reset(new FiberPool(plan[0], [dev] { (void)hipSetDevice(dev); }, n_long));
     if (getenv("SC_SERVER_LOG")) { ctx->pool->set_diag(true); ctx->wake_hist = new std::atomic<long>[24](); ctx->t_created = now_ms(); ctx->n_fast = plan[0] - n_long; ctx->n_long = n_long; }
-    if (ctx->poll_exec) {
-        ctx->polled.reset(new std::atomic<uint8_t>[ctx->workers.size()]());
+    if (watch) {
+        ctx->watch.reset(new StampWatch(ctx->workers.size()));
         ctx->pool->set_poll([ctx] { return ctx->poll_stamps(); });
     } else if (stream_count > 1) {
         ctx->server = std::thread([ctx] { ctx->serve_levels(); });
     }
+    if (ctx->resident)
+        ctx->heart = std::thread([ctx] {
+            unsigned beats = 0;
+            while (!ctx->heart_stop.load(std::memory_order_acquire)) {
+                __atomic_fetch_add(&ctx->ctl_h->heartbeat, 1u, __ATOMIC_RELEASE);
+                if (ctx->watch && (++beats % 50u) == 0) ctx->poll_health();
+                std::this_thread::sleep_for(std::chrono::milliseconds(20));
+            }
+        });
     ctx->fibers_left.store(stream_count, std::memory_order_release);
     for (auto& w : ctx->workers) {
         Worker* p = w.get();

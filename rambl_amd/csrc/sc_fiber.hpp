@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -338,6 +339,55 @@ private:
     bool diag_ = false;
     std::atomic<uint64_t> busy_fast_{0}, busy_long_{0};
     std::atomic<long> hist_[2][40] = {};
+};
+
+// Fibers parked until a completion stamp -- a counter in memory that something other than the host advances (a GPU
+// kernel) -- reaches the value they wait for, seen by the pool's poll (set_poll).  One slot per fiber that may wait; the
+// callers pass in where a slot's stamp is, what makes its fiber ready and when its wait has failed.  Whoever makes a
+// fiber ready has taken its flag first, so that happens exactly once per arm().
+class StampWatch {
+public:
+    explicit StampWatch(size_t n) : slots_(new Slot[n]), n_(n) {}
+    // The fiber of slot i, once everything the watchers read for it is published; then ensure_poller() and park().
+    void arm(size_t i, unsigned want) {
+        slots_[i].want.store(want, std::memory_order_release);
+        slots_[i].flag.store(1, std::memory_order_seq_cst);
+    }
+    unsigned want(size_t i) const { return slots_[i].want.load(std::memory_order_acquire); }
+    // stamp(i): the address of slot i's stamp; ready(i) once it reads want(i).  Returns whether some slot still waits.
+    template <class Stamp, class Ready> bool poll(Stamp&& stamp, Ready&& ready) {
+        bool waiting = false;
+        for (size_t i = 0; i < n_; i++) {
+            auto seen = [&] { return __atomic_load_n(stamp(i), __ATOMIC_ACQUIRE) == want(i); };
+            if (!armed(i)) continue;
+            if (seen() && claim(i, seen)) ready(i); else waiting = true;
+        }
+        return waiting;
+    }
+    // failure(i, want): nullptr while slot i's stamp may still come, else why it will not; then fail(i, why).
+    template <class Failure, class Fail> void check(Failure&& failure, Fail&& fail) {
+        for (size_t i = 0; i < n_; i++) {
+            const char* why = nullptr;
+            auto failed = [&] { return (why = failure(i, want(i))) != nullptr; };
+            if (armed(i) && failed() && claim(i, failed)) fail(i, why);
+        }
+    }
+
+private:
+    struct Slot { std::atomic<unsigned> want{0}; std::atomic<uint8_t> flag{0}; };     // flag 1: parked, nobody has claimed it
+    bool armed(size_t i) const { return slots_[i].flag.load(std::memory_order_acquire) == 1; }
+    // Takes slot i's flag if over() still holds with the flag in hand.  The flag may be one the fiber raised for a LATER
+    // wait than the one judged (another thread judged the same, took the flag first, and the fiber ran on and armed
+    // again); nothing changes under a held flag, so looking again decides.
+    template <class Over> bool claim(size_t i, Over&& over) {
+        uint8_t one = 1;
+        if (!slots_[i].flag.compare_exchange_strong(one, 0, std::memory_order_acq_rel)) return false;      // another thread has it
+        if (over()) return true;
+        slots_[i].flag.store(1, std::memory_order_seq_cst);
+        return false;
+    }
+    std::unique_ptr<Slot[]> slots_;
+    size_t n_;
 };
 
 }  // namespace sc

@@ -1747,8 +1747,7 @@ int level_kind(const LevelHdr& h) {
     const int S = h.S, Q = h.Q, Rn = h.e1 - h.e0;
     const bool chain = h.mode == MODE_SAMPLE && h.n_sweeps > 0 && S > 1 && Rn > 0;
     if (!chain) return 0;
-    static const bool rows_lds_allowed = !(getenv("SC_ROWS_LDS") && atoi(getenv("SC_ROWS_LDS")) == 0);     // measurements: rows in HBM everywhere
-    const bool wl = rows_lds_allowed && ((long)Q * chain_w_stride(S) + 16) * 4 <= (long)CHAINW_ROWS_BYTES;
+    const bool wl = ((long)Q * chain_w_stride(S) + 16) * 4 <= (long)CHAINW_ROWS_BYTES;
     int nb = (S + 15) / 16;
     nb = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
     return 1 + 2 * (nb - 1) + (wl ? 1 : 0);
@@ -1772,8 +1771,6 @@ int level_lds_kb(const LevelHdr& h, int K) {
     return (int)((need + 1023) / 1024);
 }
 static size_t batch_lds(const LevelBatch& b, int n) {
-    static const bool exact = !(getenv("SC_LDS_EXACT") && atoi(getenv("SC_LDS_EXACT")) == 0);
-    if (!exact) return LDS_TOTAL;
     int kb = 0;
     for (int i = 0; i < n; i++) { const int k = (b.it[i].kind >> 8) & 0xFFFF; kb = k > kb ? k : kb; }
     size_t bytes = (size_t)kb * 1024;

@@ -2,7 +2,8 @@
 // completes their levels.  Usage: fiber_check R T LEVELS [TL [poll]].  Prints one line of counters; exit 0 when every fiber
 // has walked all its levels, no more than T fibers ever ran at once, and the process never had more than T + 2 threads.
 // With a fifth argument the server only STAMPS the levels (as the GPU does) and the executors find the stamps themselves
-// (FiberPool::set_poll, the way resident contexts run): a fiber raises its flag, asks for a watcher and parks.
+// (FiberPool::set_poll over the library's StampWatch, the way resident contexts run): a fiber arms its slot, asks for a
+// watcher and parks.
 #include <dirent.h>
 
 #include <atomic>
@@ -30,9 +31,7 @@ static int thread_count() {
 struct Region {
     Fiber* f = nullptr;
     std::atomic<int> state{0};       // 1: level posted, 2: done
-    std::atomic<int> stamp{0};       // poll mode: the number of the last level the "device" has finished (a sequence, never reset)
-    std::atomic<int> want{0};        // poll mode: the number of the level the fiber waits for
-    std::atomic<unsigned char> flag{0};   // poll mode: parked until the stamp is seen
+    unsigned stamp = 0;               // poll mode: the number of the last level the "device" has finished (a sequence, never reset)
     long levels_done = 0;
     double acc = 0;                   // something on the fiber's stack frame must survive the migrations
 };
@@ -42,6 +41,7 @@ int main(int argc, char** argv) {
     const int TL = argc > 4 ? atoi(argv[4]) : 0;            // of the T threads: those that take the `later` fibers first
     const bool poll = argc > 5;
     std::vector<Region> regs((size_t)R);
+    StampWatch watch((size_t)R);
     std::mutex mu;
     std::vector<Region*> posted;
     std::atomic<int> finished{0};
@@ -51,19 +51,8 @@ int main(int argc, char** argv) {
         FiberPool pool(T, nullptr, TL);
         if (poll)
             pool.set_poll([&] {
-                bool waiting = false;
-                for (Region& r : regs) {
-                    if (r.flag.load(std::memory_order_acquire) != 1) continue;
-                    if (r.stamp.load(std::memory_order_acquire) != r.want.load(std::memory_order_acquire)) { waiting = true; continue; }
-                    unsigned char one = 1;
-                    if (!r.flag.compare_exchange_strong(one, 0)) continue;
-                    // (the flag may by now be the one of the region's NEXT level -- another thread saw this stamp first and the
-                    // region ran on: with the flag in hand, look again)
-                    if (r.stamp.load(std::memory_order_acquire) != r.want.load(std::memory_order_acquire)) { r.flag.store(1); waiting = true; continue; }
-                    r.state.store(2, std::memory_order_release);
-                    pool.make_ready(r.f);
-                }
-                return waiting;
+                return watch.poll([&](size_t i) { return &regs[i].stamp; },
+                                  [&](size_t i) { regs[i].state.store(2, std::memory_order_release); pool.make_ready(regs[i].f); });
             });
         // the level server: takes what was posted, "runs" it, makes the fiber ready again
         std::thread server([&] {
@@ -71,7 +60,7 @@ int main(int argc, char** argv) {
             while (!stop.load()) {
                 { std::lock_guard<std::mutex> lk(mu); mine.swap(posted); }
                 for (Region* r : mine) {
-                    if (poll) { r->stamp.store(r->want.load(std::memory_order_acquire), std::memory_order_release); continue; }      // the executors will see it
+                    if (poll) { __atomic_store_n(&r->stamp, watch.want((size_t)(r - regs.data())), __ATOMIC_RELEASE); continue; }      // the executors will see it
                     r->state.store(2, std::memory_order_release); pool.make_ready(r->f);
                 }
                 mine.clear();
@@ -89,14 +78,14 @@ int main(int argc, char** argv) {
                 int caught = 0;
                 for (int lv = 0; lv < L; lv++) {
                     r->state.store(1, std::memory_order_release);
-                    r->want.store(lv + 1, std::memory_order_release);
+                    if (poll) watch.arm((size_t)i, (unsigned)lv + 1);
                     { std::lock_guard<std::mutex> lk(mu); posted.push_back(r); }
-                    if (poll) { r->flag.store(1, std::memory_order_seq_cst); pool.ensure_poller(); }
+                    if (poll) pool.ensure_poller();
                     // the protocol of the library: whoever completes the level makes the fiber ready exactly once, so the
                     // fiber parks exactly once per level -- also when the level is already done by now
                     FiberPool::park();
                     if (r->state.load(std::memory_order_acquire) != 2) { r->levels_done = -1000000; break; }
-                    if (poll && r->stamp.load(std::memory_order_acquire) != lv + 1) { r->levels_done = -2000000; break; }      // woken before its level was done
+                    if (poll && __atomic_load_n(&r->stamp, __ATOMIC_ACQUIRE) != (unsigned)lv + 1) { r->levels_done = -2000000; break; }      // woken before its level was done
                     local[lv & 63] += 1.0;
                     r->levels_done++;
                     // long double bookkeeping and a C++ exception thrown and caught inside the fiber, wherever it runs by now

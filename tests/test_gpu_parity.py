@@ -12,9 +12,16 @@ pytestmark = pytest.mark.gpu
 # 312: log-likelihoods below -745 for every candidate at a soft-update level (fp64 exp underflow); 465: NaN
 # abundances in the reference itself; 744: every candidate pruned before the end of the gene (the reference
 # prints nothing and exits 0); 7705: a single-character strain label against a two-character read label (the
-# reference's never-set count -> log 0)
-@pytest.mark.parametrize("seed", list(range(0, 16)) + [312, 465, 744, 7705])
-def test_region_parity(seed, tmp_path, oracle_bin):
+# reference's never-set count -> log 0).  "resident": the same region on a resident level worker of a context with one
+# slot (SC_RESIDENT=1), which watches its stamps on its own thread instead of launching every level
+_SEEDS = list(range(0, 16)) + [312, 465, 744, 7705]
+
+
+@pytest.mark.parametrize("seed, resident", [(s, False) for s in _SEEDS] + [(1, True)],
+                         ids=[str(s) for s in _SEEDS] + ["1-resident"])
+def test_region_parity(seed, resident, tmp_path, oracle_bin, monkeypatch):
+    if resident:
+        monkeypatch.setenv("SC_RESIDENT", "1")
     d = str(tmp_path)
     args = T.make_case(seed, d)
     exp_fa, exp_tr = T.run_oracle(args, d, trace=True)
