@@ -159,6 +159,20 @@ int sc_roi_edge_support(sc_ctx* ctx, int handle, int* support, int cap, int* n_e
 int sc_roi_thread_tables(sc_ctx* ctx, int handle, int* count, int* first_read, int cls_cap, int* pool, long pool_cap,
                          char* symbols, int* n_cls, long* n_pool);
 
+/* Row a14 on its own, for tests: one sampler level (the Polya-urn draws of np_bayes_clustering,
+ * NonparametricClustering.cpp:230-249) through the production level kernel, on chosen inputs and
+ * chosen uniforms.  S (2..128) strains with urn weights a0[S] and read log-likelihood rows
+ * ll[s*n_reads + r], present where has[r] != 0; the level's n_ent entries (read ent_rid, copy number
+ * ent_cn, one-symbol label ent_sym < 16) start at entry index e0 (the entries in front name other
+ * reads); mates as a CSR over the reads (mate_off[n_reads+1], mate_idx, -1: none); n_sweeps sweeps,
+ * draw t taking U[t] (n_u >= n_sweeps * sum ent_cn <= 40000).  Out: kdraw[S] draws per strain,
+ * cnt[S*16] draws per (strain, read symbol), out[5] = draws, draws of the fp64 scan tier, draws of
+ * the literal tier, window passes, kernel variant.  Only on a context of one stream (SC_ERR_ARG
+ * otherwise: resident level workers run the same level body). */
+int sc_sample_level(sc_ctx* ctx, int S, const double* a0, int n_reads, const double* ll, const unsigned char* has,
+                    int n_ent, int e0, const int* ent_rid, const int* ent_cn, const int* ent_sym, const int* mate_off,
+                    const int* mate_idx, int n_sweeps, const double* U, int n_u, unsigned* kdraw, unsigned* cnt, long* out);
+
 /* ---- rows a2-a4 on the host: the alignment file and a window's reads (rambl_amd/csrc/sc_ingest.cpp) ----------
  *
  * The reference shells out to samtools for every window (StrainCall.cpp:496 `view -q mq -F 1804 region`, :696

@@ -142,8 +142,9 @@ static void normalize_ld(ld *f, int n) {                               /* Nonpar
 }
 
 /* std::discrete_distribution<int>(p.begin(),p.end())(gen): libstdc++
- * <bits/random.tcc> param_type::_M_initialize + operator(). */
-static int discrete_draw(const ld *p, int S, MT *gen, double *prob, double *cp) {
+ * <bits/random.tcc> param_type::_M_initialize + operator(), with the uniform
+ * generate_canonical<double,53>(gen) given: `u` (not looked at when S < 2). */
+static int discrete_draw_u(const ld *p, int S, double u, double *prob, double *cp) {
     if (S < 2) return 0;                               /* no random number consumed */
     for (int i = 0; i < S; i++) prob[i] = (double)p[i];
     double sum = 0.0;
@@ -152,7 +153,6 @@ static int discrete_draw(const ld *p, int S, MT *gen, double *prob, double *cp) 
     double acc = 0.0;
     for (int i = 0; i < S; i++) { acc = (i == 0) ? prob[0] : acc + prob[i]; cp[i] = acc; }
     cp[S - 1] = 1.0;
-    double u = mt_canonical(gen);
     int lo = 0, len = S;                               /* std::lower_bound */
     while (len > 0) {
         int half = len >> 1, mid = lo + half;
@@ -160,6 +160,33 @@ static int discrete_draw(const ld *p, int S, MT *gen, double *prob, double *cp) 
         else len = half;
     }
     return lo;
+}
+static int discrete_draw(const ld *p, int S, MT *gen, double *prob, double *cp) {
+    return discrete_draw_u(p, S, S < 2 ? 0.0 : mt_canonical(gen), prob, cp);
+}
+
+/* The draw loop of np_bayes_clustering (NonparametricClustering.cpp:230-249):
+ * n sweeps over the draw slots q = 0..Q-1 (read rid[q], mate uid[q] or -1) with
+ * the urn weights a[] (updated in place).  Draw t = i * Q + q takes the uniform
+ * U[t] -- the reference's generate_canonical<double,53>(mt19937(1234)) stream --
+ * and its choice goes to choice[t].  p: [S] long double, prob / cp: [S] double. */
+static void urn_draw_loop(Strain *st, int S, ld *a, const int *rid, const int *uid, int Q, int n, const double *U,
+                          int *choice, ld *p, double *prob, double *cp) {
+    long t = 0;
+    for (int i = 0; i < n; i++) {
+        for (int q = 0; q < Q; q++, t++) {
+            for (int s = 0; s < S; s++) p[s] = a[s];
+            normalize_ld(p, S);
+            for (int s = 0; s < S; s++) {
+                p[s] = logl(p[s]) + strain_logprob_id(&st[s], rid[q]);
+                if (uid[q] >= 0 && st[s].has[uid[q]]) p[s] += strain_logprob_id(&st[s], uid[q]);
+                p[s] = expl(p[s]);
+            }
+            int c = discrete_draw_u(p, S, U[t], prob, cp);
+            a[c] += 1;
+            choice[t] = c;
+        }
+    }
 }
 
 typedef struct {
@@ -227,27 +254,28 @@ static void np_bayes_clustering(ClusterCtx *cx, StrainVec *strains, RBVec *reads
     int read_size = 0;
     for (int j = 0; j < m; j++) read_size += reads->v[j].cn;
     n = n < 40000 / read_size ? n : 40000 / read_size;
-    for (int i = 0; i < n; i++) {
-        for (int j = 0; j < m; j++) {
-            int id = reads->v[j].rid;
-            for (int cn = reads->v[j].cn; cn > 0; cn--) {
-                for (int s = 0; s < S; s++) p[s] = a[s];
-                normalize_ld(p, S);
-                for (int s = 0; s < S; s++) {
-                    Strain *st = &strains->v[s];
-                    p[s] = logl(p[s]) + strain_logprob_id(st, id);
-                    int uid = rp_get(cx->rp, id, cn - 1);
-                    if (uid >= 0 && st->has[uid]) p[s] += strain_logprob_id(st, uid);
-                    p[s] = expl(p[s]);
-                }
-                int c = discrete_draw(p, S, &gen, prob, cp);
-                cx->draws++;
-                a[c] += 1;
-                Strain *sc_st = &strains->v[c];
-                sc_add(&sc[c], sc_st->path.v[sc_st->path.n - 1]->lab, reads->v[j].lab, 1);
-            }
+    /* the draw slots in draw order: (read, copy cn .. 1) */
+    int *rid = (int *)xmalloc(sizeof(int) * (size_t)read_size), *uid = (int *)xmalloc(sizeof(int) * (size_t)read_size);
+    const char **lab = (const char **)xmalloc(sizeof(char *) * (size_t)read_size);
+    for (int j = 0, q = 0; j < m; j++)
+        for (int cn = reads->v[j].cn; cn > 0; cn--, q++) {
+            rid[q] = reads->v[j].rid;
+            uid[q] = rp_get(cx->rp, reads->v[j].rid, cn - 1);
+            lab[q] = reads->v[j].lab;
         }
+    const long total = (long)n * read_size;
+    double *U = (double *)xmalloc(sizeof(double) * (size_t)(total > 0 ? total : 1));
+    U[0] = 0.0;
+    int *choice = (int *)xmalloc(sizeof(int) * (size_t)(total > 0 ? total : 1));
+    for (long t = 0; t < total; t++) U[t] = S < 2 ? 0.0 : mt_canonical(&gen);
+    urn_draw_loop(strains->v, S, a, rid, uid, read_size, n, U, choice, p, prob, cp);
+    cx->draws += total;
+    for (long t = 0; t < total; t++) {
+        int c = choice[t];
+        Strain *sc_st = &strains->v[c];
+        sc_add(&sc[c], sc_st->path.v[sc_st->path.n - 1]->lab, lab[t % read_size], 1);
     }
+    free(rid); free(uid); free(lab); free(U); free(choice);
     normalize_ld(a, S);
     for (int s = 0; s < S; s++) a[s] *= read_size;
     for (int s = 0; s < S; s++) for (int k = 0; k < sc[s].n; k++) sc[s].v[k].v /= n;

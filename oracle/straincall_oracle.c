@@ -147,6 +147,86 @@ void oracle_mt_canonical(unsigned seed, int n, double *out) {
     for (int i = 0; i < n; i++) out[i] = mt_canonical(&m);
 }
 
+/* One sampler level's draws (the draw loop of np_bayes_clustering) on chosen
+ * inputs and uniforms.  S strains with urn weights a0[S] and read
+ * log-likelihood rows ll[s * n_reads + r] (widened to long double, as the
+ * reference holds them), present where has[r] != 0; the level's Q draw slots
+ * in draw order: read rid[q], mate uid[q] (-1: none), read symbol sym[q]
+ * (0..n_sym-1); n_sweeps sweeps, draw t = i * Q + q taking U[t].  Out:
+ * choice[n_sweeps * Q], kdraw[S] (draws per strain), cnt[S * n_sym] (draws per
+ * strain and read symbol).  Returns 0, or -1 on an argument out of range. */
+int oracle_urn_draws(int S, const double *a0, int n_reads, const double *ll, const unsigned char *has, int Q,
+                     const int *rid, const int *uid, const int *sym, int n_sym, int n_sweeps, const double *U,
+                     int *choice, long *kdraw, long *cnt) {
+    if (S < 1 || n_reads < 1 || Q < 1 || n_sweeps < 0 || n_sym < 1) return -1;
+    for (int q = 0; q < Q; q++)
+        if (rid[q] < 0 || rid[q] >= n_reads || uid[q] < -1 || uid[q] >= n_reads || sym[q] < 0 || sym[q] >= n_sym) return -1;
+    Strain *st = (Strain *)xmalloc(sizeof(Strain) * (size_t)S);
+    ld *a = (ld *)xmalloc(sizeof(ld) * (size_t)S), *p = (ld *)xmalloc(sizeof(ld) * (size_t)S);
+    double *prob = (double *)xmalloc(sizeof(double) * (size_t)S), *cp = (double *)xmalloc(sizeof(double) * (size_t)S);
+    for (int s = 0; s < S; s++) {
+        memset(&st[s], 0, sizeof(Strain));
+        st[s].nreads = n_reads;
+        st[s].rll = (ld *)xmalloc(sizeof(ld) * (size_t)n_reads);
+        st[s].has = (unsigned char *)xmalloc((size_t)n_reads);
+        for (int r = 0; r < n_reads; r++) {
+            st[s].has[r] = has[r] != 0;
+            st[s].rll[r] = has[r] ? (ld)ll[(long)s * n_reads + r] : 0;
+        }
+        a[s] = a0[s];
+    }
+    urn_draw_loop(st, S, a, rid, uid, Q, n_sweeps, U, choice, p, prob, cp);
+    for (int s = 0; s < S; s++) kdraw[s] = 0;
+    for (long i = 0; i < (long)S * n_sym; i++) cnt[i] = 0;
+    for (long t = 0; t < (long)n_sweeps * Q; t++) {
+        kdraw[choice[t]]++;
+        cnt[(long)choice[t] * n_sym + sym[t % Q]]++;
+    }
+    for (int s = 0; s < S; s++) { free(st[s].rll); free(st[s].has); }
+    free(st); free(a); free(p); free(prob); free(cp);
+    return 0;
+}
+
+/* The same level through np_bayes_clustering itself (its own mt19937(1234)
+ * stream): reads ent_rid[n_ent] with copy numbers ent_cn and one-symbol labels
+ * ent_sym (index into "ACGT-="), mates as a CSR over the reads; ll / has / a0 as
+ * above.  abund_out[S] receives the level's abundances (normalized urn
+ * weights times the number of draw slots).  Returns 0, or -1 on bad input. */
+int oracle_np_bayes_level(int S, const double *a0, int n_reads, const double *ll, const unsigned char *has, int n_ent,
+                          const int *ent_rid, const int *ent_cn, const int *ent_sym, const int *mate_off,
+                          const int *mate_idx, int n_sweeps, double *abund_out) {
+    static char labs[6][2] = { "A", "C", "G", "T", "-", "=" };
+    if (S < 1 || n_reads < 1 || n_ent < 1 || n_sweeps < 1) return -1;
+    for (int r = 0; r < n_ent; r++)
+        if (ent_rid[r] < 0 || ent_rid[r] >= n_reads || ent_cn[r] < 1 || ent_sym[r] < 0 || ent_sym[r] >= 6) return -1;
+    Node node; memset(&node, 0, sizeof node); node.lab = labs[0];
+    StrainVec sv; vec_init(sv);
+    for (int s = 0; s < S; s++) {
+        Strain st; strain_init(&st, 100, 0.01L, n_reads);
+        for (int r = 0; r < n_reads; r++) { st.has[r] = has[r] != 0; st.rll[r] = has[r] ? (ld)ll[(long)s * n_reads + r] : 0; }
+        st.abundance = a0[s];
+        vec_push(st.path, &node);
+        vec_push(sv, st);
+    }
+    RBVec reads; vec_init(reads);
+    for (int r = 0; r < n_ent; r++) { RB b = { ent_rid[r], labs[ent_sym[r]], ent_cn[r] }; vec_push(reads, b); }
+    ReadPairs rp; rp.n = n_reads; rp.mates = (IntVec *)xmalloc(sizeof(IntVec) * (size_t)n_reads);
+    for (int r = 0; r < n_reads; r++) {
+        vec_init(rp.mates[r]);
+        for (int k = mate_off[r]; k < mate_off[r + 1]; k++) vec_push(rp.mates[r], mate_idx[k]);
+    }
+    ClusterCtx cx; memset(&cx, 0, sizeof cx); cx.rp = &rp;
+    ld *ab = NULL;
+    np_bayes_clustering(&cx, &sv, &reads, n_sweeps, &ab);
+    for (int s = 0; s < S; s++) abund_out[s] = (double)ab[s];
+    free(ab);
+    for (int s = 0; s < S; s++) strain_free(&sv.v[s]);
+    vec_free(sv); vec_free(reads);
+    for (int r = 0; r < n_reads; r++) vec_free(rp.mates[r]);
+    free(rp.mates);
+    return 0;
+}
+
 #ifndef ORACLE_NO_MAIN
 int main(int argc, char **argv) { return oracle_main(argc, argv); }
 #endif

@@ -63,6 +63,9 @@ def load_library():
     lib.sc_roi_edge_support.argtypes = [vp, C.c_int, ip, C.c_int, ip]
     lib.sc_msa_align.argtypes = [vp, cp, ip, C.c_int, C.c_char_p, C.c_long, ip]
     lib.sc_roi_thread_tables.argtypes = [vp, C.c_int, ip, ip, C.c_int, ip, C.c_long, C.c_char_p, ip, C.POINTER(C.c_long)]
+    dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint)
+    lib.sc_sample_level.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.POINTER(C.c_ubyte), C.c_int, C.c_int, ip, ip, ip, ip, ip,
+                                    C.c_int, dp, C.c_int, up, up, C.POINTER(C.c_long)]
     pi, pc, pu = C.POINTER(ip), C.POINTER(C.c_char_p), C.POINTER(C.c_ubyte)
     lib.sc_aln_open.argtypes = [cp, C.POINTER(vp)]
     lib.sc_aln_open_filtered.argtypes = [cp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(vp)]
@@ -83,14 +86,14 @@ def load_library():
     for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
-              "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables"):
+              "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level"):
         getattr(lib, f).restype = C.c_int
     return lib
 
 
 EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "sc_host_plan", "sc_host_bind", "sc_roi_submit", "sc_roi_wait", "sc_roi_result",
            "sc_roi_graph_dump", "sc_roi_trace", "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align",
-           "sc_roi_thread_tables", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
+           "sc_roi_thread_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
            "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs"]
 
 
@@ -389,6 +392,37 @@ class Context:
         if rc != SC_OK:
             raise self._err(rc)
         return list(cnt[:ncls.value]), list(first[:ncls.value]), list(pool[:npool.value]), sym.raw
+
+    def sample_level(self, a0, ll, has, ent_rid, ent_cn, ent_sym, mates, n_sweeps, U, e0=1):
+        """Row a14 on its own (a test entry): one sampler level through the production kernel with the uniforms `U`.
+        ll: [S][n_reads] log-likelihoods, has: [n_reads] presence, mates: per read a list of mate ids (-1: none).
+        Returns dict(kdraw[S], cnt[S][16], n_draws, n_slow, n_exact, n_pass, kind)."""
+        import numpy as np
+        a0 = np.ascontiguousarray(a0, dtype=np.float64)
+        ll = np.ascontiguousarray(ll, dtype=np.float64)
+        S, n_reads = ll.shape
+        assert a0.shape == (S,)
+        has = np.ascontiguousarray(has, dtype=np.uint8)
+        assert has.shape == (n_reads,)
+        ent = [np.ascontiguousarray(x, dtype=np.int32) for x in (ent_rid, ent_cn, ent_sym)]
+        assert ent[0].shape == ent[1].shape == ent[2].shape
+        mate_off = np.zeros(n_reads + 1, dtype=np.int32)
+        mate_off[1:] = np.cumsum([len(mates[r]) if r < len(mates) else 0 for r in range(n_reads)])
+        mate_idx = np.array([m for r in range(min(len(mates), n_reads)) for m in mates[r]] or [0], dtype=np.int32)
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        kdraw = np.zeros(S, dtype=np.uint32)
+        cnt = np.zeros((S, 16), dtype=np.uint32)
+        out = (C.c_long * 5)()
+
+        def ptr(x, t):
+            return x.ctypes.data_as(C.POINTER(t))
+        rc = self.lib.sc_sample_level(self.h, S, ptr(a0, C.c_double), n_reads, ptr(ll, C.c_double), ptr(has, C.c_ubyte),
+                                      len(ent[0]), e0, ptr(ent[0], C.c_int), ptr(ent[1], C.c_int), ptr(ent[2], C.c_int),
+                                      ptr(mate_off, C.c_int), ptr(mate_idx, C.c_int), n_sweeps, ptr(U, C.c_double), len(U),
+                                      ptr(kdraw, C.c_uint), ptr(cnt, C.c_uint), out)
+        if rc != SC_OK:
+            raise self._err(rc)
+        return dict(kdraw=kdraw, cnt=cnt, n_draws=out[0], n_slow=out[1], n_exact=out[2], n_pass=out[3], kind=out[4])
 
     def msa_align(self, seqs):
         """Row a7: rows of the progressive sum-of-pairs MSA of `seqs` (in the given order)."""

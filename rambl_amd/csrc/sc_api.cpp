@@ -2120,6 +2120,112 @@ int sc_roi_thread_tables(sc_ctx* h, int handle, int* count, int* first_read, int
     std::memcpy(symbols, job->thr_sym.data(), std::min<size_t>(8, job->thr_sym.size()));
     return SC_OK;
 }
+int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const double* ll, const unsigned char* has, int n_ent,
+                    int e0, const int* ent_rid, const int* ent_cn, const int* ent_sym, const int* mate_off, const int* mate_idx,
+                    int n_sweeps, const double* U, int n_u, unsigned* kdraw, unsigned* cnt, long* out) {
+    if (!h || !a0 || !ll || !has || !ent_rid || !ent_cn || !ent_sym || !mate_off || !U || !kdraw || !cnt || !out) return SC_ERR_ARG;
+    Ctx* ctx = &h->c;
+    // the resident workers run the same level body; this entry launches the level itself
+    if (ctx->resident || ctx->workers.size() != 1) return SC_ERR_ARG;
+    if (S < 2 || S > MAXS || n_reads < 1 || n_ent < 1 || e0 < 0 || e0 > (1 << 20) || n_sweeps < 1) return SC_ERR_ARG;
+    for (int s = 0; s < S; s++) if (!(a0[s] >= 0.0) || !std::isfinite(a0[s])) return SC_ERR_ARG;
+    long Q = 0;
+    for (int r = 0; r < n_ent; r++) {
+        if (ent_rid[r] < 0 || ent_rid[r] >= n_reads || ent_cn[r] < 1 || ent_sym[r] < 0 || ent_sym[r] >= KMAX) return SC_ERR_ARG;
+        Q += ent_cn[r];
+    }
+    if (Q * n_sweeps > MAX_DRAWS || n_u < Q * n_sweeps) return SC_ERR_ARG;
+    for (long t = 0; t < Q * n_sweeps; t++) if (!(U[t] >= 0.0 && U[t] <= 1.0)) return SC_ERR_ARG;
+    if (mate_off[0] != 0) return SC_ERR_ARG;
+    for (int r = 0; r < n_reads; r++) if (mate_off[r + 1] < mate_off[r]) return SC_ERR_ARG;
+    const int nm = mate_off[n_reads];
+    if (nm > 0 && !mate_idx) return SC_ERR_ARG;
+    for (int i = 0; i < nm; i++) if (mate_idx[i] < -1 || mate_idx[i] >= n_reads) return SC_ERR_ARG;
+    try {
+        HIPCHK(hipSetDevice(ctx->device));
+        Worker w;                                      // a private worker: own stream, own parameter / result blocks
+        w.ctx = ctx;
+        w.init();
+        w.stage = &w.passthrough;
+        w.passthrough.on = false;
+        struct Free {
+            Worker& w;
+            ~Free() { (void)hipHostFree(w.Ph); (void)hipFree(w.Pd); (void)hipHostFree(w.Rh); (void)hipEventDestroy(w.sync_ev); (void)hipStreamDestroy(w.st); }
+        } free_w{w};
+        // entries [0, e0) belong to other levels: they name other reads (the last ones, backwards), so that an entry index
+        // that misses e0 reads the wrong row
+        const int E = e0 + n_ent;
+        std::vector<int> rid((size_t)E), cn((size_t)E, 1), lab_off((size_t)E), lab_len((size_t)E, 1), qoff((size_t)E, 0);
+        std::vector<uint8_t> first((size_t)E, 1), labels((size_t)E + 1);
+        labels[(size_t)E] = 0;                         // the strains' node label (read only by the update, which does not run)
+        for (int e = 0; e < E; e++) {
+            const int r = e - e0;
+            rid[(size_t)e] = r >= 0 ? ent_rid[r] : n_reads - 1 - e % n_reads;
+            lab_off[(size_t)e] = e;
+            labels[(size_t)e] = (uint8_t)(r >= 0 ? ent_sym[r] : 0);
+        }
+        for (int r = 0, q = 0; r < n_ent; r++) { cn[(size_t)(e0 + r)] = ent_cn[r]; qoff[(size_t)(e0 + r)] = q; q += ent_cn[r]; }
+        const hipStream_t st = w.st;
+        JobDev jd{};
+        jd.ent_rid = upload(w.passthrough, w.b_ent_rid, rid, st);
+        jd.ent_cn = upload(w.passthrough, w.b_ent_cn, cn, st);
+        jd.ent_lab_off = upload(w.passthrough, w.b_ent_lab_off, lab_off, st);
+        jd.ent_lab_len = upload(w.passthrough, w.b_ent_lab_len, lab_len, st);
+        jd.ent_first = upload(w.passthrough, w.b_ent_first, first, st);
+        jd.ent_qoff = upload(w.passthrough, w.b_ent_qoff, qoff, st);
+        jd.labels = upload(w.passthrough, w.b_labels, labels, st);
+        const std::vector<int> mptr(mate_off, mate_off + n_reads + 1), midx(mate_idx, mate_idx + nm);      // (alive until the copies are done)
+        jd.mate_ptr = upload(w.passthrough, w.b_mate_ptr, mptr, st);
+        jd.mate_idx = upload(w.passthrough, w.b_mate_idx, midx, st);
+        jd.n_reads = n_reads; jd.K = KMAX; jd.code_N = KMAX;
+        // rows as in the region set-up; strain s lives in row slot(s), not in row s
+        auto slot = [](int s) { return (s * 37 + 5) % MAXS; };
+        jd.ll_stride = ((long)n_reads + 3) & ~3L;
+        std::vector<double> rows((size_t)jd.ll_stride * MAXS, 0.0);
+        for (int s = 0; s < S; s++) std::memcpy(&rows[(size_t)slot(s) * jd.ll_stride], ll + (size_t)s * n_reads, sizeof(double) * n_reads);
+        jd.ll = upload(w.passthrough, w.b_ll, rows, st);
+        std::vector<uint8_t> hv(has, has + n_reads);
+        hv.resize((size_t)n_reads + 8, 0);
+        jd.has = upload(w.passthrough, w.b_has, hv, st);
+        // the uniforms, padded by 2048 values as sc_ctx_create pads its stream (the chain stages windows of 1024)
+        std::vector<double> u(U, U + Q * n_sweeps);
+        u.resize((size_t)(Q * n_sweeps + 2048), 0.5);
+        std::vector<float> uf(u.begin(), u.end());
+        DevBuf b_u, b_uf;
+        jd.U = upload(w.passthrough, b_u, u, st);
+        jd.Uf = upload(w.passthrough, b_uf, uf, st);
+        const long qcap = std::max<long>(Q, 1);
+        jd.isnew = (uint8_t*)w.b_isnew.ensure((size_t)n_ent + 8);
+        jd.qcap = qcap;
+        jd.tabA = (double*)w.b_tabA.ensure(sizeof(double) * (size_t)qcap * MAXS);
+        jd.tabLf = (float*)w.b_tabLf.ensure(sizeof(float) * (size_t)(std::min<long>(qcap, MAX_DRAWS) + 4) * 136);
+        jd.qcode = (uint8_t*)w.b_qcode.ensure((size_t)qcap + 8);
+        jd.qent = (int*)w.b_qent.ensure(sizeof(int) * (size_t)qcap);
+        jd.quid = (int*)w.b_quid.ensure(sizeof(int) * (size_t)qcap);
+        const JobDev* jd_dev = (const JobDev*)w.b_jobdev.ensure(sizeof(JobDev));
+        HIPCHK(hipMemcpyAsync((void*)jd_dev, &jd, sizeof jd, hipMemcpyHostToDevice, st));
+
+        LevelParams& P = *w.Ph;
+        for (int s = 0; s < S; s++) P.sp[s] = StrainParam{slot(s), E, 1, 0, a0[s], 0.0};
+        LevelHdr H{};
+        H.mode = MODE_SAMPLE; H.S = S; H.e0 = e0; H.e1 = E; H.Q = (int)Q; H.n_sweeps = n_sweeps;
+        H.n_copy = 0; H.do_update = 0; H.seq = 1;
+        std::memset(w.Rh, 0, sizeof(LevelResult));
+        const int kind = level_kind(H);
+        LevelBatch batch;
+        batch.it[0] = LevelItem{jd_dev, H, kind | (level_lds_kb(H, KMAX) << 8), w.Pm, w.Rd};
+        launch_level_batch(st, kind, batch, 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        const LevelResult& R = *w.Rh;
+        if (R.seq != 1u || R.error) throw ScError(SC_ERR_INTERNAL, "the sampler level did not complete");
+        for (int s = 0; s < S; s++) kdraw[s] = R.kdraw[s];
+        std::memcpy(cnt, R.cnt, sizeof(unsigned) * (size_t)S * KMAX);
+        out[0] = (long)R.n_draws; out[1] = (long)R.n_slow; out[2] = (long)R.n_exact; out[3] = (long)R.n_pass; out[4] = kind;
+        return SC_OK;
+    } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
+    catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
+}
 int sc_roi_release(sc_ctx* h, int handle) {
     if (!h) return SC_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->c.mu);

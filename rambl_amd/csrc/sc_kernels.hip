@@ -393,8 +393,13 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
         // boundary; once it clears the lower margin there is nothing above the target to test.
         const float alt = tgt - (T - alast * llast);
         const float epsT = EPSW * T;
-        const float lim_up = fmaf(uf, posf, epsT);           // a boundary at / above the target moves down by <= u per earlier draw
-        const float lim_dn = fmaf(1.0f - uf, posf, epsT);    // one below it moves up by <= 1 - u
+        // a boundary at / above the target moves down by <= u per earlier draw, one below it up by <= 1 - u.  The pass
+        // knows u only as its fp32 copy uf (|u - uf| <= 2^-25: 1 - uf can lie below 1 - u, uf below u) and forms the
+        // limits in fp32: 2^-22 per earlier draw covers both.  (That slack is absolute, per draw of weight <= 1, so
+        // eps * T does not cover it once T is small: 100 draws of u = 1e-9 in front of a u = 1 - 1.25 * 2^-24, which
+        // reads 1 - 2^-24, at T = 0.1 -- tests/test_sampler_tiers.py)
+        const float lim_up = fmaf(uf + 0x1p-22f, posf, epsT);
+        const float lim_dn = fmaf((1.0f + 0x1p-22f) - uf, posf, epsT);
         // NaN (flagged slot) and T == 0 fail the test
         const bool okl = (__uint_as_float(dn) >= lim_dn) && ((__uint_as_float(up) >= lim_up) || (alt >= lim_dn));
         const unsigned long long F = ~__ballot(okl);
