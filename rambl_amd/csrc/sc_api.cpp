@@ -400,7 +400,7 @@ extern "C" int sc_host_plan(int stream_count, int local_world, double cpus, int*
 namespace sc {
 
 struct Worker {
-    Ctx* ctx;
+    Ctx* ctx = nullptr;
     Fiber* fib = nullptr;
     int slot = 0;                     // worker index
     hipStream_t st = nullptr;         // a setup stream of the context (not owned), or a private one (own_stream)
@@ -423,7 +423,7 @@ struct Worker {
     LevelParams* Pd = nullptr;        // device copy, only for the grid kernels of very large levels
     LevelResult* Rh = nullptr;        // host-mapped, written by the kernel, stamped last
     LevelResult* Rd = nullptr;
-    bool own_blocks = false;          // Ph / Pd / Rh are this worker's own allocations (sc_msa_align's private worker)
+    bool own_blocks = false;          // Ph / Pd / Rh are this worker's own allocations (a private worker: init_private)
     unsigned seq = 0;                 // stamp of the last level launched (the level server waits for it)
     DevBuf b_ent_rid, b_ent_cn, b_ent_lab_off, b_ent_lab_len, b_ent_first, b_ent_qoff, b_labels, b_mate_ptr, b_mate_idx,
         b_ll, b_has, b_isnew, b_tabA, b_tabLf, b_qcode, b_qent, b_quid, b_out_ptr, b_out_node, b_pool_ptr, b_pool_rid,
@@ -438,7 +438,9 @@ struct Worker {
     bool setup_held = false;          // this region holds one of the context's set-up places
     std::vector<ld> cnt_scratch;      // [MAXS][KMAX] draws per (strain, read symbol) of the level just sampled
 
+    ~Worker();
     void init();
+    void init_private(Ctx* c);
     void run();
     void process(Job& job);
     void complete_level(const LevelItem& it, bool timed);
@@ -448,7 +450,18 @@ struct Worker {
     int msa_device(const std::vector<std::string>& seqs, std::vector<std::string>& rows);
     void thread_device(const std::string& G, const std::vector<AlignedRead>& R, const std::vector<std::vector<CigarOp>>& cig,
                        ThreadTables& T);
+    JobDev job_dev(PinnedArena& ar, const FlatGraph& f, const std::vector<int>& ent_qoff, const std::vector<int>& mate_off,
+                   const std::vector<int>& mate_idx, int n_reads, long qcap, int max_entries);
+    LevelItem level_item(const JobDev* job, const LevelHdr& H, int K) const {
+        return LevelItem{job, H, level_kind(H) | (level_lds_kb(H, K) << 8), Pm, Rd};
+    }
     void cluster(Job& job, const PoGraph& g, FlatGraph& f);
+};
+// The mailbox a region walks its levels on (resident workers): handed on after its last level, or by an exception.
+struct MailHold {
+    Worker* w;
+    void drop() { const int m = w->mslot.load(std::memory_order_relaxed); if (m >= 0) { w->mslot.store(-1, std::memory_order_release); w->ctx->release_mailbox(m); } }
+    ~MailHold() { drop(); }
 };
 
 void Worker::init() {
@@ -465,6 +478,20 @@ void Worker::init() {
     HIPCHK(hipHostGetDevicePointer((void**)&Rd, Rh, 0));
     std::memset(Rh, 0, sizeof(LevelResult));
     cnt_scratch.assign((size_t)MAXS * KMAX, 0);
+}
+// A worker outside the context's slots, for an entry that may run while regions are in flight: its own stream and
+// parameter / result blocks, its copies passed through.
+void Worker::init_private(Ctx* c) {
+    ctx = c;
+    init();
+    stage = &passthrough;
+    passthrough.on = false;
+}
+Worker::~Worker() {
+    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+    if (sync_ev) (void)hipEventDestroy(sync_ev);
+    if (st && own_stream) (void)hipStreamDestroy(st);
+    if (own_blocks) { (void)hipHostFree(Ph); (void)hipFree(Pd); (void)hipHostFree(Rh); }
 }
 
 // Everything this worker has put on its set-up stream is done.  The stream is shared with other regions, so the wait is
@@ -1050,200 +1077,171 @@ static void fmt_g17(std::string& out, double v) {
     out += b;
 }
 
-void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
-    const int n_reads = (int)job.reads.size();
-    const double t_cluster0 = now_ms();
-    ev_used = 0;
-    const sc_params& pa = job.params;
-    const ld e = (ld)pa.error_rate, tau = (ld)pa.tau, diff = (ld)pa.diff_rate;     // float widened, StrainCall.cpp:58-154
-    const int K = f.K;
-
-    // ---- pseudo level holding every read once, for read_assign (NonparametricClustering.cpp:776-836)
-    const int final_e0 = (int)f.ent_rid.size();
-    long total_copies = 0;
-    {
-        int qo = 0;
-        for (int i = 0; i < n_reads; i++) {
-            f.ent_rid.push_back(i); f.ent_cn.push_back(job.reads[i].cn); f.ent_lab_off.push_back(0);
-            f.ent_lab_len.push_back(0); f.ent_first.push_back(1);
-            qo += job.reads[i].cn;
-        }
-        total_copies = qo;
-    }
-    // prefix of copy numbers inside each level
-    std::vector<int>& ent_qoff = ent_qoff_buf;                           // (the slot's: reused from region to region)
-    ent_qoff.assign(f.ent_rid.size(), 0);
-    int max_level_entries = n_reads, max_level_q = 0;
-    for (int l = 0; l < f.n_levels; l++) {
-        int qo = 0;
-        for (int x = f.level_ent_ptr[l]; x < f.level_ent_ptr[l + 1]; x++) { ent_qoff[x] = qo; qo += f.ent_cn[x]; }
-        max_level_entries = std::max(max_level_entries, f.level_ent_ptr[l + 1] - f.level_ent_ptr[l]);
-        max_level_q = std::max(max_level_q, qo);
-    }
-    { int qo = 0; for (int i = 0; i < n_reads; i++) { ent_qoff[final_e0 + i] = qo; qo += job.reads[i].cn; } }
-    const long qcap = std::max<long>(std::max<long>(max_level_q, total_copies), 1);
-    // cells of a read_loglik row that can hold a value when level l starts: the reads of the levels before it and their
-    // mates (the soft update enters a mate the first time it is asked for, Strain.cpp:147-150) -- a prefix of the read ids
-    std::vector<int> level_hi((size_t)f.n_levels + 1, 0);
-    for (int l = 0; l < f.n_levels; l++) {
-        int hi = level_hi[(size_t)l];
-        for (int x = f.level_ent_ptr[l]; x < f.level_ent_ptr[l + 1]; x++) {
-            const int rid = f.ent_rid[x];
-            hi = std::max(hi, rid + 1);
-            for (int k = job.mate_off[(size_t)rid]; k < job.mate_off[(size_t)rid + 1]; k++) hi = std::max(hi, job.mate_idx[(size_t)k] + 1);
-        }
-        level_hi[(size_t)l + 1] = hi;
-    }
-
-    // ---- upload the static arrays
+// The region's device block without what the caller sets itself (ll, has, U, Uf): the level-major entries of `f`, their
+// copy-number prefixes `ent_qoff` and the mates uploaded through `ar`, the level kernels' scratch sized for `qcap` draw
+// slots and `max_entries` entries at one level.
+JobDev Worker::job_dev(PinnedArena& ar, const FlatGraph& f, const std::vector<int>& ent_qoff, const std::vector<int>& mate_off,
+                       const std::vector<int>& mate_idx, int n_reads, long qcap, int max_entries) {
     JobDev jd{};
-    jd.ent_rid = upload(*stage, b_ent_rid, f.ent_rid, st);
-    jd.ent_cn = upload(*stage, b_ent_cn, f.ent_cn, st);
-    jd.ent_lab_off = upload(*stage, b_ent_lab_off, f.ent_lab_off, st);
-    jd.ent_lab_len = upload(*stage, b_ent_lab_len, f.ent_lab_len, st);
-    jd.ent_first = upload(*stage, b_ent_first, f.ent_first, st);
-    jd.ent_qoff = upload(*stage, b_ent_qoff, ent_qoff, st);
-    jd.labels = upload(*stage, b_labels, f.labels, st);
-    jd.mate_ptr = upload(*stage, b_mate_ptr, job.mate_off, st);
-    jd.mate_idx = upload(*stage, b_mate_idx, job.mate_idx, st);
-    jd.n_reads = n_reads; jd.K = K; jd.code_N = f.code_N;
+    jd.ent_rid = upload(ar, b_ent_rid, f.ent_rid, st);
+    jd.ent_cn = upload(ar, b_ent_cn, f.ent_cn, st);
+    jd.ent_lab_off = upload(ar, b_ent_lab_off, f.ent_lab_off, st);
+    jd.ent_lab_len = upload(ar, b_ent_lab_len, f.ent_lab_len, st);
+    jd.ent_first = upload(ar, b_ent_first, f.ent_first, st);
+    jd.ent_qoff = upload(ar, b_ent_qoff, ent_qoff, st);
+    jd.labels = upload(ar, b_labels, f.labels, st);
+    jd.mate_ptr = upload(ar, b_mate_ptr, mate_off, st);
+    jd.mate_idx = upload(ar, b_mate_idx, mate_idx, st);
+    jd.n_reads = n_reads; jd.K = f.K; jd.code_N = f.code_N;
     jd.ll_stride = ((long)n_reads + 3) & ~3L;
-    jd.ll = (double*)b_ll.ensure(sizeof(double) * (size_t)jd.ll_stride * MAXS);
-    jd.has = (uint8_t*)b_has.ensure((size_t)n_reads + 8);
-    HIPCHK(hipMemsetAsync(jd.has, 0, (size_t)n_reads + 8, st));
-    jd.U = ctx->dU;
-    jd.Uf = ctx->dUf;
-    jd.isnew = (uint8_t*)b_isnew.ensure((size_t)max_level_entries + 8);
+    jd.isnew = (uint8_t*)b_isnew.ensure((size_t)max_entries + 8);
     jd.qcap = qcap;
     jd.tabA = (double*)b_tabA.ensure(sizeof(double) * (size_t)qcap * MAXS);
     jd.tabLf = (float*)b_tabLf.ensure(sizeof(float) * (size_t)(std::min<long>(qcap, MAX_DRAWS) + 4) * 136);
     jd.qcode = (uint8_t*)b_qcode.ensure((size_t)qcap + 8);
     jd.qent = (int*)b_qent.ensure(sizeof(int) * (size_t)qcap);
     jd.quid = (int*)b_quid.ensure(sizeof(int) * (size_t)qcap);
-    // the batched level kernels find the region through a pointer: the block travels once, with the uploads
-    const JobDev* jd_dev = (const JobDev*)b_jobdev.ensure(sizeof(JobDev));
-    stage->h2d((void*)jd_dev, &jd, sizeof jd, st);
+    return jd;
+}
 
-    // ---- a16: every edge support on the device
-    {
-        std::vector<int> esrc(f.out_node.size());
-        for (int a = 0; a < f.n_nodes; a++) for (int x = f.out_ptr[a]; x < f.out_ptr[a + 1]; x++) esrc[x] = a;
-        int* d_out_ptr = upload(*stage, b_out_ptr, f.out_ptr, st);
-        int* d_out_node = upload(*stage, b_out_node, f.out_node, st);
-        int* d_pool_ptr = upload(*stage, b_pool_ptr, f.pool_ptr, st);
-        int* d_pool_rid = upload(*stage, b_pool_rid, f.pool_rid, st);
-        int* d_pool_cn = upload(*stage, b_pool_cn, f.pool_cn, st);
-        uint8_t* d_isend = upload(*stage, b_isend, f.node_is_end, st);
-        int* d_esrc = upload(*stage, b_esrc, esrc, st);
-        int* d_sup = (int*)b_support.ensure(sizeof(int) * std::max<size_t>(esrc.size(), 1));
-        launch_edge_support(st, d_out_ptr, d_out_node, d_pool_ptr, d_pool_rid, d_pool_cn, d_isend, d_esrc, (int)esrc.size(),
-                            f.pools_sorted ? 1 : 0, d_sup);
-        if (!esrc.empty())
-            stage->d2h(f.out_support.data(), d_sup, sizeof(int) * esrc.size(), st);
-        const double t_sync0 = now_ms();
-        sync_stream();
-        stage->land();
-        if (stage != &passthrough) ctx->release_arena(stage);      // every transfer of the set-up is done
-        stage = &passthrough;
-        if (getenv("SC_SYNC_LOG")) fprintf(stderr, "sync uploads+edge_support %.3f ms (since cluster start %.3f)\n", now_ms() - t_sync0, now_ms() - t_cluster0);
-        job.edge_support = f.out_support;
-    }
+// The level walk of one region: streaming_clustering (NonparametricClustering.cpp:262-582), then read_assign
+// (:776-836).  It keeps the candidates' bookkeeping on the host and hands each level to the GPU on the worker's slot.
+// Its buffers are reused from level to level: no allocation per level.
+struct LevelWalk {
+    Worker& w;
+    Job& job;
+    const FlatGraph& f;
+    const JobDev& jd;                 // the region's device block, and its copy on the device
+    const JobDev* jd_dev;
+    const std::vector<int>& level_hi; // per level: the prefix of read ids a read_loglik row can hold (Worker::cluster)
+    const int final_e0;               // the pseudo level of read_assign: one entry per read from here on
+    const long total_copies;
+    MailHold& mail;
+    const sc_params& pa;
+    const ld e, tau, diff;            // float widened, StrainCall.cpp:58-154
+    const int K, n_reads;
+    const bool want_trace;
+    const LevelResult* const Rh;      // the slot's results, host-mapped
 
-    // ---- level walk: from here on the region's host work is a few microseconds per level
-    if (setup_held) { ctx->setup_leave(); setup_held = false; }
-    job.stats.setup_ms = now_ms() - t_cluster0;
-    struct MailHold {                  // the mailbox the region walks on (resident workers): taken now, handed on when the walk ends
-        Worker* w;
-        void drop() { const int m = w->mslot.load(std::memory_order_relaxed); if (m >= 0) { w->mslot.store(-1, std::memory_order_release); w->ctx->release_mailbox(m); } }
-        ~MailHold() { drop(); }
-    } mail_hold{this};
-    if (ctx->resident) {
-        const double t_m0 = now_ms();
-        mslot.store(ctx->acquire_mailbox(this), std::memory_order_release);
-        job.stats.mailbox_ms = now_ms() - t_m0;
-        __atomic_store_n(&Rh->seq, 0u, __ATOMIC_RELEASE);       // (stamps are the mailbox's from here on: never 0)
-    }
-    std::vector<HStrain> level_strains, sub_strains;
     std::vector<Model> models;                                           // pool; free entries in free_models
-    std::vector<int> free_models;
-    auto model_new = [&]() { if (!free_models.empty()) { const int m = free_models.back(); free_models.pop_back(); return m; }
-                             models.emplace_back(); return (int)models.size() - 1; };
-    auto drop = [&](const HStrain& s, std::vector<int>& free_slots_) { free_slots_.push_back(s.slot); free_models.push_back(s.model); };
+    std::vector<int> free_models, free_slots;                            // (free_slots: read_loglik rows no candidate holds)
     std::vector<PathRec> arena;
-    std::vector<int> free_slots;
-    for (int i = MAXS - 1; i >= 0; i--) free_slots.push_back(i);
-    std::vector<HStrain> final_strains;
-    std::string& tr = job.trace;
-    const bool want_trace = pa.want_trace != 0;
-
-    auto strain_seq = [&](const HStrain& s) {
-        std::vector<int> rev;
-        for (int t = s.tail; t >= 0; t = arena[t].parent) rev.push_back(arena[t].node);
-        std::string q;
-        for (auto it = rev.rbegin(); it != rev.rend(); ++it) q += f.node_label_str[*it];
-        return q;
-    };
-    auto trace_dump = [&](const char* when, int level, const std::vector<HStrain>& sv) {
-        if (!want_trace || sv.empty()) return;
-        tr += "------------------------------\n"; tr += when; tr += "\nlevel: "; tr += std::to_string(level); tr += "\n";
-        for (const auto& s : sv) { tr += strain_seq(s); tr += "\t"; fmt_g17(tr, (double)s.abundance); tr += "\n"; }
-    };
-    auto sort_strains = [&](std::vector<HStrain>& sv) {                  // std::sort, abundance descending
-        std::vector<int> perm(sv.size());
-        for (size_t i = 0; i < sv.size(); i++) perm[i] = (int)i;
-        std_sort_perm(perm, [&](int a, int b) { return sv[a].abundance > sv[b].abundance; });
-        std::vector<HStrain> t;
-        t.reserve(sv.size());
-        for (int i : perm) t.push_back(sv[i]);
-        sv.swap(t);
-    };
-    auto seq_identity = [](const std::string& a, const std::string& b) {  // NonparametricClustering.cpp:584-612
-        int iden = 0, len = 0;
-        for (size_t i = 0; i < a.size(); ++i) {
-            const char x = a[i], y = i < b.size() ? b[i] : 0;
-            if (x == '-' && y == '-') continue;
-            else if (x == '=' && y == '=') continue;
-            else if (x == '=' && y == '-') continue;
-            else if (x == '-' && y == '=') continue;
-            else if (x == '^' && y == '^') continue;
-            else if (x == y) iden += 1;
-            len += 1;
-        }
-        return (ld)((iden + 0.0) / len);
-    };
-
-    {   // level_strains.push_back(Strain(100,e)), NonparametricClustering.cpp:281; Strain.cpp:41-71
-        HStrain s{};
-        s.model = model_new();
-        Model& m = models[(size_t)s.model];
-        m.ks = K;
-        for (int i = 0; i < K * K; i++) m.sub[i] = 0;
-        for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) m.sub[i * K + j] = (i == j) ? 100 * (1 - e) : 100 * e;
-        recount(m);
-        m.dirty = 0xFFFFu;
-        for (int a = 0; a < KMAX; a++) m.stale[a] = 0xFFFFu;
-        s.abundance = 0; s.slot = free_slots.back(); free_slots.pop_back();
-        s.tail = -1; s.node = -1; s.hash = 1469598103934665603ull; s.seqlen = 0;
-        level_strains.push_back(s);
-    }
+    std::vector<HStrain> level_strains, final_strains;
+    std::vector<std::pair<int, int>> pending_copies;                     // (src slot, dst slot) for the next launch
     bool branching = false;
-    std::vector<std::pair<int, int>> pending_copies;     // (src slot, dst slot) for the next launch
-    double sampler_ms = 0;
-    long sampler_launches = 0, level_launches = 0, draws = 0, exact = 0, slow = 0, sampler_copies = 0, sampler_strains = 0, passes = 0;
-    unsigned long long chain_cycles = 0, chain_wall = 0, level_ticks = 0, sampler_ticks = 0;
-
+    int cur_level = 0;
+    struct Cand { int parent; int node; ld abundance; };
+    std::vector<Cand> cands;                                             // buffers of the walk, reused from level to level
+    std::vector<int> first_child;
+    std::vector<HStrain> kept_buf, sub_strains;
+    int la_cache[MAXS];                                                  // the candidates' symbols, for the update after the level
     // where the host's time between two levels goes (sc_stats.host_us): [0] parameters of the level (log tables, the
     // host-mapped block), [1] results of the level into the candidates' models, pruning, [2] extension of the candidates
-    int la_cache[MAXS];
     double host_acc[3] = {0, 0, 0};
-    double t_mark = now_ms();
-    auto lap = [&](int k) { const double t = now_ms(); host_acc[k] += t - t_mark; t_mark = t; };
-    double t_last_done = now_ms();
-    FILE* level_log = getenv("SC_LEVEL_LOG") ? fopen((std::string(getenv("SC_LEVEL_LOG")) + "." + std::to_string(slot)).c_str(), "a") : nullptr;   // diagnostics only
-    int cur_level = 0;
-    auto run_level = [&](int mode, int e0, int e1, int Q, int n_sweeps, bool do_update, const std::vector<HStrain>& sv,
-                         bool has_dups, bool any_multi) {
-        LevelParams& P = *Ph;
+    double t_mark, t_last_done;
+    FILE* level_log;                                                     // SC_LEVEL_LOG: diagnostics only
+
+    LevelWalk(Worker& w, Job& job, const FlatGraph& f, const JobDev& jd, const JobDev* jd_dev, const std::vector<int>& level_hi,
+              int final_e0, long total_copies, MailHold& mail)
+        : w(w), job(job), f(f), jd(jd), jd_dev(jd_dev), level_hi(level_hi), final_e0(final_e0), total_copies(total_copies),
+          mail(mail), pa(job.params), e((ld)pa.error_rate), tau((ld)pa.tau), diff((ld)pa.diff_rate), K(f.K),
+          n_reads((int)job.reads.size()), want_trace(pa.want_trace != 0), Rh(w.Rh) {
+        w.ev_used = 0;
+        for (int i = MAXS - 1; i >= 0; i--) free_slots.push_back(i);
+        {   // level_strains.push_back(Strain(100,e)), NonparametricClustering.cpp:281; Strain.cpp:41-71
+            HStrain s{};
+            s.model = model_new();
+            Model& m = models[(size_t)s.model];
+            m.ks = K;
+            for (int i = 0; i < K * K; i++) m.sub[i] = 0;
+            for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) m.sub[i * K + j] = (i == j) ? 100 * (1 - e) : 100 * e;
+            recount(m);
+            m.dirty = 0xFFFFu;
+            for (int a = 0; a < KMAX; a++) m.stale[a] = 0xFFFFu;
+            s.abundance = 0; s.slot = free_slots.back(); free_slots.pop_back();
+            s.tail = -1; s.node = -1; s.hash = 1469598103934665603ull; s.seqlen = 0;
+            level_strains.push_back(s);
+        }
+        t_mark = t_last_done = now_ms();
+        level_log = getenv("SC_LEVEL_LOG") ? fopen((std::string(getenv("SC_LEVEL_LOG")) + "." + std::to_string(w.slot)).c_str(), "a") : nullptr;
+    }
+    ~LevelWalk() { if (level_log) fclose(level_log); }
+    // the levels in order (:284-334): their nodes, the update of the candidates (sampler once they branch), extension
+    void run() {
+        for (int level = 0; level < f.n_levels; level++) {
+            visit_nodes(level);
+            const int e0 = f.level_ent_ptr[level], e1 = f.level_ent_ptr[level + 1];
+            const int Rn = e1 - e0;
+            cur_level = level;
+            if (Rn > 0 && !level_strains.empty()) {
+                const int S = (int)level_strains.size();
+                if (S > MAXS) throw ScError(SC_ERR_CAPACITY, "more than 128 candidate strains at one level");
+                if ((long)S * K * K > (long)level_table_capacity())
+                    throw ScError(SC_ERR_UNSUPPORTED, std::to_string(S) + " candidate strains over " + std::to_string(K) +
+                                  " distinct symbols: their log tables do not fit the level kernel's LDS");
+                bool has_dups = false, any_multi = false;
+                for (int x = e0; x < e1; x++) { if (!f.ent_first[x]) has_dups = true; if (f.ent_lab_len[x] != 1) any_multi = true; }
+                for (auto& s : level_strains) if (f.node_lab_len[s.node] != 1) any_multi = true;
+                const int Q = f.level_read_count[level];
+                if (branching) np_bayes_clustering(e0, e1, Q, has_dups, any_multi);
+                else hard_clustering(e0, e1, Q, has_dups, any_multi);
+            }
+            trace_dump("after clustering", level, level_strains);
+            lap(1);
+            extend();
+            lap(2);
+        }
+        read_assign();
+        report();
+    }
+    // The nodes popped at this level: the root starts the first candidate's path; an end node runs read_reassign (only its
+    // sort has an effect, :672-702) and merge_strains (:645-670).
+    void visit_nodes(int level) {
+        const int n0 = f.level_node_ptr[level], n1 = f.level_node_ptr[level + 1];
+        for (int x = n0; x < n1; x++) {
+            trace_dump("before clustering", level, level_strains);
+            const int u = f.level_nodes[x];
+            if (u == 0) {
+                if (level_strains.empty()) throw ScError(SC_ERR_INTERNAL, "no strain at the root");
+                HStrain& s = level_strains[0];
+                arena.push_back({0, s.tail});
+                s.tail = (int)arena.size() - 1; s.node = 0;
+                s.hash = hash_extend(s.hash, f.node_label_str[0]); s.seqlen += (int)f.node_label_str[0].size();
+                s.abundance = 1;
+            } else if (f.node_is_end[u]) {
+                // Every candidate pruned before the end of the gene: the reference runs into undefined behaviour here
+                // (merged(1, strains[0]) of an empty vector, :650) and in practice prints nothing and exits 0; so does
+                // this path (no contig for the region).
+                if (level_strains.empty()) { final_strains.clear(); continue; }
+                // sorted twice, as the reference does (read_reassign, then merge_strains): std_sort_perm is not stable
+                sort_strains(level_strains);
+                sort_strains(level_strains);
+                std::vector<std::string> seqs;
+                for (auto& s : level_strains) seqs.push_back(path_seq(s, false));
+                std::vector<int> merged{0};
+                for (int i = 1; i < (int)level_strains.size(); i++) {
+                    size_t j;
+                    for (j = 0; j < merged.size(); j++)
+                        if (seq_identity(seqs[i], seqs[merged[j]]) > 1 - diff) {
+                            level_strains[merged[j]].abundance += level_strains[i].abundance;
+                            break;
+                        }
+                    if (j == merged.size()) merged.push_back(i);
+                }
+                std::vector<HStrain> kept;
+                std::vector<char> keep(level_strains.size(), 0);
+                for (int j : merged) { kept.push_back(level_strains[j]); keep[j] = 1; }
+                for (size_t i = 0; i < level_strains.size(); i++) if (!keep[i]) drop(level_strains[i]);
+                level_strains.swap(kept);
+                final_strains = level_strains;
+            }
+        }
+    }
+    // One level on the GPU: its parameters into the slot's host-mapped block, the level handed over and waited for
+    // (Worker::complete_level), its figures counted into job.stats.
+    void run_level(int mode, int e0, int e1, int Q, int n_sweeps, bool do_update, const std::vector<HStrain>& sv,
+                              bool has_dups, bool any_multi) {
+        LevelParams& P = *w.Ph;
         const int S = (int)sv.size();
         LevelHdr H{};
         H.mode = mode; H.S = S; H.e0 = e0; H.e1 = e1; H.has_dups = has_dups; H.any_multi = any_multi; H.Q = Q;
@@ -1301,39 +1299,41 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
             std::memcpy(dst, hm.lpc, sizeof(double) * (size_t)K * K);
         }
         const bool chain = (mode == MODE_SAMPLE) && S > 1 && n_sweeps > 0;
-        const bool timed = chain && pa.want_timing && !ctx->resident;      // (no launch to bracket with events when the workers are resident)
+        const bool timed = chain && pa.want_timing && !w.ctx->resident;      // (no launch to bracket with events when the workers are resident)
         if (level_wants_grid(jd, H)) {
             // a very large level: row copies / the single-symbol update on a grid, from a device copy of the parameters
             const size_t bytes = offsetof(LevelParams, lpt) + sizeof(double) * (size_t)S * K * K;
-            HIPCHK(hipMemcpyAsync(Pd, Ph, bytes, hipMemcpyHostToDevice, st));
-            H.done = launch_level_grid(st, jd, H, Pd, Rd);
-            sync_stream();                               // the level's kernel runs on another stream
+            HIPCHK(hipMemcpyAsync(w.Pd, w.Ph, bytes, hipMemcpyHostToDevice, w.st));
+            H.done = launch_level_grid(w.st, jd, H, w.Pd, w.Rd);
+            w.sync_stream();                             // the level's kernel runs on another stream
         }
-        const int ms = mslot.load(std::memory_order_relaxed);
-        H.seq = ms >= 0 ? ++ctx->mail_seq[(size_t)ms] : ++seq;     // (a mailbox keeps its own count: regions take turns on it)
+        const int ms = w.mslot.load(std::memory_order_relaxed);
+        H.seq = ms >= 0 ? ++w.ctx->mail_seq[(size_t)ms] : ++w.seq;     // (a mailbox keeps its own count: regions take turns on it)
         if (timed) {
             // a fresh pair of events per sampler launch; their times are read after the walk, not between levels
-            if (ev_used + 2 > ev_pool.size()) {
+            if (w.ev_used + 2 > w.ev_pool.size()) {
                 hipEvent_t a = nullptr, b = nullptr;
                 HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-                ev_pool.push_back(a); ev_pool.push_back(b);
+                w.ev_pool.push_back(a); w.ev_pool.push_back(b);
             }
-            ev0 = ev_pool[ev_used]; ev1 = ev_pool[ev_used + 1];
-            ev_used += 2;
+            w.ev0 = w.ev_pool[w.ev_used]; w.ev1 = w.ev_pool[w.ev_used + 1];
+            w.ev_used += 2;
         }
         const double t_launched = level_log ? now_ms() : 0.0;
         lap(0);
-        const int kind = level_kind(H);
-        complete_level(LevelItem{jd_dev, H, kind | (level_lds_kb(H, K) << 8), Pm, Rd}, timed);
+        const LevelItem it = w.level_item(jd_dev, H, K);
+        w.complete_level(it, timed);
         t_mark = now_ms();                                   // (the wait for the level is not host work)
-        level_launches++;
+        sc_stats& stats = job.stats;
+        stats.level_launches++;
         if (chain) {
-            sampler_launches++; sampler_copies += Q;
-            draws += (long)Rh->n_draws; exact += (long)Rh->n_exact; slow += (long)Rh->n_slow; sampler_strains += S; passes += (long)Rh->n_pass;
-            chain_cycles += Rh->chain_cycles; chain_wall += Rh->chain_wall;
+            stats.sampler_launches++; stats.sampler_read_copies += Q;
+            stats.draws += (long)Rh->n_draws; stats.exact_draws += (long)Rh->n_exact; stats.slow_draws += (long)Rh->n_slow;
+            stats.sampler_strains += S; stats.chain_passes += (long)Rh->n_pass;
+            stats.chain_cycles += (long)Rh->chain_cycles; stats.chain_wall_ticks += (long)Rh->chain_wall;
         }
-        level_ticks += Rh->level_wall;
-        if (chain) sampler_ticks += Rh->level_wall;
+        stats.level_kernel_ticks += (long)Rh->level_wall;
+        if (chain) stats.sampler_level_ticks += (long)Rh->level_wall;
         if (level_log) {
             const double t_done = now_ms();
             fprintf(level_log, "h %d mode %d S %d Q %d n %d level_us %.1f chain_us %.1f cyc %llu passes %llu slow %llu xcc %d ncopy %d multi %d "
@@ -1341,174 +1341,116 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
                     n_sweeps, Rh->level_wall * 0.01, chain ? Rh->chain_wall * 0.01 : 0.0, chain ? (unsigned long long)Rh->chain_cycles : 0ull,
                     chain ? (unsigned long long)Rh->n_pass : 0ull, chain ? (unsigned long long)Rh->n_slow : 0ull, Rh->xcc, H.n_copy, (int)any_multi,
                     Rh->phase_ticks[0] * 0.01, Rh->phase_ticks[1] * 0.01, Rh->phase_ticks[2] * 0.01, Rh->phase_ticks[3] * 0.01, Rh->phase_ticks[4] * 0.01,
-                    1e3 * (t_launched - t_last_done), 1e3 * (t_done - t_launched), 1e3 * (t_batch_launched - t_launched), batch_n);
+                    1e3 * (t_launched - t_last_done), 1e3 * (t_done - t_launched), 1e3 * (w.t_batch_launched - t_launched), w.batch_n);
             t_last_done = t_done;
         }
-        job.stats.xcd_levels[Rh->xcc & 7]++;
-        job.stats.kind_levels[std::min(std::max(kind, 0), 16)]++;
-    };
-
-    struct Cand { int parent; int node; ld abundance; };
-    std::vector<Cand> cands;                                  // buffers of the walk, reused from level to level
-    std::vector<int> first_child;
-    std::vector<HStrain> kept_buf;
-    for (int level = 0; level < f.n_levels; level++) {
-        const int n0 = f.level_node_ptr[level], n1 = f.level_node_ptr[level + 1];
-        for (int x = n0; x < n1; x++) {
-            trace_dump("before clustering", level, level_strains);
-            const int u = f.level_nodes[x];
-            if (u == 0) {
-                if (level_strains.empty()) throw ScError(SC_ERR_INTERNAL, "no strain at the root");
-                HStrain& s = level_strains[0];
-                arena.push_back({0, s.tail});
-                s.tail = (int)arena.size() - 1; s.node = 0;
-                s.hash = hash_extend(s.hash, f.node_label_str[0]); s.seqlen += (int)f.node_label_str[0].size();
-                s.abundance = 1;
-            } else if (f.node_is_end[u]) {
-                // read_reassign (only its sort has an effect, :672-702), merge_strains (:645-670)
-                // Every candidate pruned before the end of the gene: the reference runs into undefined behaviour here
-                // (merged(1, strains[0]) of an empty vector, :650) and in practice prints nothing and exits 0; so does
-                // this path (no contig for the region).
-                if (level_strains.empty()) { final_strains.clear(); continue; }
-                sort_strains(level_strains);
-                sort_strains(level_strains);
-                std::vector<std::string> seqs;
-                for (auto& s : level_strains) seqs.push_back(strain_seq(s));
-                std::vector<int> merged{0};
-                for (int i = 1; i < (int)level_strains.size(); i++) {
-                    size_t j;
-                    for (j = 0; j < merged.size(); j++)
-                        if (seq_identity(seqs[i], seqs[merged[j]]) > 1 - diff) {
-                            level_strains[merged[j]].abundance += level_strains[i].abundance;
-                            break;
-                        }
-                    if (j == merged.size()) merged.push_back(i);
-                }
-                std::vector<HStrain> kept;
-                std::vector<char> keep(level_strains.size(), 0);
-                for (int j : merged) { kept.push_back(level_strains[j]); keep[j] = 1; }
-                for (size_t i = 0; i < level_strains.size(); i++) if (!keep[i]) drop(level_strains[i], free_slots);
-                level_strains.swap(kept);
-                final_strains = level_strains;
+        stats.xcd_levels[Rh->xcc & 7]++;
+        stats.kind_levels[std::min(std::max(it.kind & 0xFF, 0), 16)]++;
+    }
+    // np_bayes_clustering, :128-244 (+ pruning :404-454)
+    void np_bayes_clustering(int e0, int e1, int Q, bool has_dups, bool any_multi) {
+        const int S = (int)level_strains.size();
+        const int n = std::min(pa.sweeps_cap, pa.draw_budget / Q);
+        int last[MAXS];
+        for (int s = 0; s < S; s++) {
+            last[s] = s;
+            for (int t = S - 1; t > s; t--)
+                if (level_strains[t].hash == level_strains[s].hash && level_strains[t].seqlen == level_strains[s].seqlen) { last[s] = t; break; }
+        }
+        ld prior[MAXS], post[MAXS], a[MAXS];
+        for (int s = 0; s < S; s++) prior[s] = level_strains[last[s]].abundance;
+        run_level(MODE_SAMPLE, e0, e1, Q, n, true, level_strains, has_dups, any_multi);
+        ld (*cnt)[KMAX] = reinterpret_cast<ld (*)[KMAX]>(w.cnt_scratch.data());     // (not thread_local: the fiber changes threads)
+        for (int s = 0; s < S; s++) {                      // (cold caches: see run_level)
+            const Model& m_ = models[(size_t)level_strains[s].model];
+            __builtin_prefetch(&Rh->cnt[s * KMAX]);
+            if ((s & 15) == 0) __builtin_prefetch(&Rh->kdraw[s]);
+            __builtin_prefetch(&m_.comp[0]); __builtin_prefetch(&m_.comp[4]); __builtin_prefetch(&m_.stale[0]);
+            const int la = la_cache[s];
+            if (la >= 0 && la < K) { __builtin_prefetch(&m_.sub[la * K]); __builtin_prefetch(&m_.sub[la * K + 4]); }
+        }
+        for (int s = 0; s < S; s++) for (int b = 0; b < K; b++) cnt[s][b] = 0;
+        if (S == 1 || n <= 0) {
+            // a single weight consumes no random numbers (libstdc++ discrete_distribution)
+            a[0] = level_strains[0].abundance;
+            for (int s = 1; s < S; s++) a[s] = level_strains[s].abundance;
+            if (n > 0) {
+                const long tot = (long)n * Q;
+                a[0] = sc_add_ones(a[0], (unsigned long)tot);
+                for (int x = e0; x < e1; x++)
+                    if (f.ent_lab_len[x] == 1) cnt[0][f.labels[f.ent_lab_off[x]]] += (ld)n * f.ent_cn[x];
+            }
+        } else {
+            for (int s = 0; s < S; s++) {
+                a[s] = sc_add_ones(level_strains[s].abundance, Rh->kdraw[s]);     // a[c] += 1 per draw, :195 (one rounding per draw)
+                for (int b = 0; b < K; b++) cnt[s][b] = (ld)Rh->cnt[s * KMAX + b];
             }
         }
-        const int e0 = f.level_ent_ptr[level], e1 = f.level_ent_ptr[level + 1];
-        const int Rn = e1 - e0;
-        cur_level = level;
-        if (Rn > 0 && !level_strains.empty()) {
-            const int S = (int)level_strains.size();
-            if (S > MAXS) throw ScError(SC_ERR_CAPACITY, "more than 128 candidate strains at one level");
-            if ((long)S * K * K > (long)level_table_capacity())
-                throw ScError(SC_ERR_UNSUPPORTED, std::to_string(S) + " candidate strains over " + std::to_string(K) +
-                              " distinct symbols: their log tables do not fit the level kernel's LDS");
-            bool has_dups = false, any_multi = false;
-            for (int x = e0; x < e1; x++) { if (!f.ent_first[x]) has_dups = true; if (f.ent_lab_len[x] != 1) any_multi = true; }
-            for (auto& s : level_strains) if (f.node_lab_len[s.node] != 1) any_multi = true;
-            const int Q = f.level_read_count[level];
-            if (branching) {
-                // np_bayes_clustering, :128-244 (+ pruning :404-454)
-                const int n = std::min(pa.sweeps_cap, pa.draw_budget / Q);
-                int last[MAXS];
-                for (int s = 0; s < S; s++) {
-                    last[s] = s;
-                    for (int t = S - 1; t > s; t--)
-                        if (level_strains[t].hash == level_strains[s].hash && level_strains[t].seqlen == level_strains[s].seqlen) { last[s] = t; break; }
-                }
-                ld prior[MAXS], post[MAXS], a[MAXS];
-                for (int s = 0; s < S; s++) prior[s] = level_strains[last[s]].abundance;
-                run_level(MODE_SAMPLE, e0, e1, Q, n, true, level_strains, has_dups, any_multi);
-                ld (*cnt)[KMAX] = reinterpret_cast<ld (*)[KMAX]>(cnt_scratch.data());     // (not thread_local: the fiber changes threads)
-                for (int s = 0; s < S; s++) {                      // (cold caches: see run_level)
-                    const Model& m_ = models[(size_t)level_strains[s].model];
-                    __builtin_prefetch(&Rh->cnt[s * KMAX]);
-                    if ((s & 15) == 0) __builtin_prefetch(&Rh->kdraw[s]);
-                    __builtin_prefetch(&m_.comp[0]); __builtin_prefetch(&m_.comp[4]); __builtin_prefetch(&m_.stale[0]);
-                    const int la = la_cache[s];
-                    if (la >= 0 && la < K) { __builtin_prefetch(&m_.sub[la * K]); __builtin_prefetch(&m_.sub[la * K + 4]); }
-                }
-                for (int s = 0; s < S; s++) for (int b = 0; b < K; b++) cnt[s][b] = 0;
-                if (S == 1 || n <= 0) {
-                    // a single weight consumes no random numbers (libstdc++ discrete_distribution)
-                    a[0] = level_strains[0].abundance;
-                    for (int s = 1; s < S; s++) a[s] = level_strains[s].abundance;
-                    if (n > 0) {
-                        const long tot = (long)n * Q;
-                        a[0] = sc_add_ones(a[0], (unsigned long)tot);
-                        for (int x = e0; x < e1; x++)
-                            if (f.ent_lab_len[x] == 1) cnt[0][f.labels[f.ent_lab_off[x]]] += (ld)n * f.ent_cn[x];
-                    }
-                } else {
-                    for (int s = 0; s < S; s++) {
-                        a[s] = sc_add_ones(level_strains[s].abundance, Rh->kdraw[s]);     // a[c] += 1 per draw, :195 (one rounding per draw)
-                        for (int b = 0; b < K; b++) cnt[s][b] = (ld)Rh->cnt[s * KMAX + b];
-                    }
-                }
-                ld z = 0;
-                for (int s = 0; s < S; s++) z += a[s];
-                for (int s = 0; s < S; s++) a[s] /= z;
-                for (int s = 0; s < S; s++) a[s] *= Q;
-                for (int s = 0; s < S; s++) {
-                    HStrain& st_ = level_strains[s];
-                    Model& m_ = models[(size_t)st_.model];
-                    st_.abundance += a[s];                                   // update_model, Strain.cpp:106-125
-                    unsigned changed = 0;
-                    {
-                        const int la = la_cache[s];                          // the symbol of the candidate's node (single-symbol labels only)
-                        if (la >= 0 && la < K) {
-                            for (int b = 0; b < K; b++)
-                                if (cnt[s][b] > 0) { m_.sub[la * K + b] += cnt[s][b] / n; m_.stale[la] |= (uint16_t)(1u << b); }
-                            m_.dirty |= 1u << la;
-                            changed = 1u << la;
-                        }
-                    }
-                    recount_rows(m_, changed);
-                }
-                for (int s = 0; s < S; s++) post[s] = level_strains[last[s]].abundance;
-                ld A_delta_max = 0;
-                for (int s = 0; s < S; s++) { ld d = post[s] - prior[s]; if (A_delta_max < d) A_delta_max = d; }
-                ld Z = 0;
-                for (int s = 0; s < S; s++) Z += a[s];
-                const ld Zt = Z * tau;
-                std::vector<HStrain>& kept = kept_buf;               // (the walk's own: no allocation per level)
-                kept.clear();
-                for (int s = 0; s < S; s++) {
-                    const ld d = post[s] - prior[s];
-                    if (a[s] < Zt || d < 0.01 * A_delta_max) drop(level_strains[s], free_slots);
-                    else kept.push_back(level_strains[s]);
-                }
-                level_strains.swap(kept);
-            } else {
-                // hard_clustering, :17-125
-                run_level(MODE_HARD, e0, e1, Q, 0, true, level_strains, has_dups, any_multi);
-                for (int s = 0; s < S; s++) {                      // (cold caches: see run_level)
-                    const Model& m_ = models[(size_t)level_strains[s].model];
-                    for (int o = 0; o < K * K; o += 8) __builtin_prefetch(&Rh->subst[(size_t)s * K * K + o]);
-                    for (int o = 0; o < K * K; o += 4) __builtin_prefetch(&m_.sub[o]);
-                    __builtin_prefetch(&m_.comp[0]); __builtin_prefetch(&m_.comp[4]); __builtin_prefetch(&m_.stale[0]);
-                    if ((s & 7) == 0) __builtin_prefetch(&Rh->abund[s]);
-                }
-                for (int s = 0; s < S; s++) {
-                    HStrain& st_ = level_strains[s];
-                    Model& m_ = models[(size_t)st_.model];
-                    st_.abundance += (ld)Rh->abund[s];
-                    const double* sub_d = Rh->subst + (size_t)s * K * K;      // compact [K][K]
-                    unsigned changed = 0;
-                    for (int a = 0; a < K; a++)
-                        for (int b = 0; b < K; b++) {
-                            const double d = sub_d[a * K + b];
-                            if (d != 0.0) {                                   // (x + 0.0 == x for every x the counts can hold: they are never -0)
-                                m_.sub[a * K + b] += (ld)d;
-                                m_.dirty |= 1u << a; m_.stale[a] |= (uint16_t)(1u << b); changed |= 1u << a;
-                            }
-                        }
-                    recount_rows(m_, changed);
+        ld z = 0;
+        for (int s = 0; s < S; s++) z += a[s];
+        for (int s = 0; s < S; s++) a[s] /= z;
+        for (int s = 0; s < S; s++) a[s] *= Q;
+        for (int s = 0; s < S; s++) {
+            HStrain& st_ = level_strains[s];
+            Model& m_ = models[(size_t)st_.model];
+            st_.abundance += a[s];                                   // update_model, Strain.cpp:106-125
+            unsigned changed = 0;
+            {
+                const int la = la_cache[s];                          // the symbol of the candidate's node (single-symbol labels only)
+                if (la >= 0 && la < K) {
+                    for (int b = 0; b < K; b++)
+                        if (cnt[s][b] > 0) { m_.sub[la * K + b] += cnt[s][b] / n; m_.stale[la] |= (uint16_t)(1u << b); }
+                    m_.dirty |= 1u << la;
+                    changed = 1u << la;
                 }
             }
+            recount_rows(m_, changed);
         }
-        trace_dump("after clustering", level, level_strains);
-        lap(1);
-
-        // ---- candidate extension, :473-551
+        for (int s = 0; s < S; s++) post[s] = level_strains[last[s]].abundance;
+        ld A_delta_max = 0;
+        for (int s = 0; s < S; s++) { ld d = post[s] - prior[s]; if (A_delta_max < d) A_delta_max = d; }
+        ld Z = 0;
+        for (int s = 0; s < S; s++) Z += a[s];
+        const ld Zt = Z * tau;
+        std::vector<HStrain>& kept = kept_buf;               // (the walk's own: no allocation per level)
+        kept.clear();
+        for (int s = 0; s < S; s++) {
+            const ld d = post[s] - prior[s];
+            if (a[s] < Zt || d < 0.01 * A_delta_max) drop(level_strains[s]);
+            else kept.push_back(level_strains[s]);
+        }
+        level_strains.swap(kept);
+    }
+    // hard_clustering, :17-125
+    void hard_clustering(int e0, int e1, int Q, bool has_dups, bool any_multi) {
+        const int S = (int)level_strains.size();
+        run_level(MODE_HARD, e0, e1, Q, 0, true, level_strains, has_dups, any_multi);
+        for (int s = 0; s < S; s++) {                      // (cold caches: see run_level)
+            const Model& m_ = models[(size_t)level_strains[s].model];
+            for (int o = 0; o < K * K; o += 8) __builtin_prefetch(&Rh->subst[(size_t)s * K * K + o]);
+            for (int o = 0; o < K * K; o += 4) __builtin_prefetch(&m_.sub[o]);
+            __builtin_prefetch(&m_.comp[0]); __builtin_prefetch(&m_.comp[4]); __builtin_prefetch(&m_.stale[0]);
+            if ((s & 7) == 0) __builtin_prefetch(&Rh->abund[s]);
+        }
+        for (int s = 0; s < S; s++) {
+            HStrain& st_ = level_strains[s];
+            Model& m_ = models[(size_t)st_.model];
+            st_.abundance += (ld)Rh->abund[s];
+            const double* sub_d = Rh->subst + (size_t)s * K * K;      // compact [K][K]
+            unsigned changed = 0;
+            for (int a = 0; a < K; a++)
+                for (int b = 0; b < K; b++) {
+                    const double d = sub_d[a * K + b];
+                    if (d != 0.0) {                                   // (x + 0.0 == x for every x the counts can hold: they are never -0)
+                        m_.sub[a * K + b] += (ld)d;
+                        m_.dirty |= 1u << a; m_.stale[a] |= (uint16_t)(1u << b); changed |= 1u << a;
+                    }
+                }
+            recount_rows(m_, changed);
+        }
+    }
+    // candidate extension, :473-551
+    void extend() {
         branching = false;
         cands.clear();
         for (const HStrain& s : level_strains) __builtin_prefetch(&f.out_ptr[(size_t)s.node]);
@@ -1551,7 +1493,7 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
         // materialise: the first surviving child of a parent inherits its row, the others copy it
         first_child.assign(level_strains.size(), -1);
         for (int c = 0; c < (int)cands.size(); c++) if (first_child[cands[c].parent] < 0) first_child[cands[c].parent] = c;
-        for (size_t p = 0; p < level_strains.size(); p++) if (first_child[p] < 0) drop(level_strains[p], free_slots);
+        for (size_t p = 0; p < level_strains.size(); p++) if (first_child[p] < 0) drop(level_strains[p]);
         sub_strains.clear();
         for (int c = 0; c < (int)cands.size(); c++) {
             const HStrain& par = level_strains[cands[c].parent];
@@ -1573,13 +1515,12 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
         }
         level_strains.swap(sub_strains);
         sub_strains.clear();
-        lap(2);
     }
-
-    // ---- read_assign, :776-836, then the final sort, StrainCall.cpp:1027
-    std::vector<HStrain>& fs = final_strains;
-    const int S = (int)fs.size();
-    if (S > 0) {
+    // read_assign, :776-836, then the final sort, StrainCall.cpp:1027
+    void read_assign() {
+        std::vector<HStrain>& fs = final_strains;
+        const int S = (int)fs.size();
+        if (S == 0) return;
         const int Q = (int)total_copies;
         const int n = std::min(pa.sweeps_cap, pa.draw_budget / std::max(Q, 1));
         std::vector<ld> a(S);
@@ -1596,47 +1537,169 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
         // The last level is done: the mailbox goes to the next region.  What is left of this one -- its sequences, and giving
         // back what the walk has allocated (the graph, the candidates' models: milliseconds of free()) -- is a long stretch, and
         // those belong on the pool's set-up threads: on a continuation thread it would hold up ~100 levels of other regions.
-        mail_hold.drop();
-        if (ctx->split_exec && FiberPool::in_fiber()) FiberPool::yield();
+        mail.drop();
+        if (w.ctx->split_exec && FiberPool::in_fiber()) FiberPool::yield();
         ld z = 0;
         for (int s = 0; s < S; s++) z += a[s];
         for (int s = 0; s < S; s++) fs[s].abundance = a[s] / z;
         sort_strains(fs);
         for (auto& s : fs) {
-            std::string q;
-            std::vector<int> rev;
-            for (int t = s.tail; t >= 0; t = arena[t].parent) rev.push_back(arena[t].node);
-            for (auto it = rev.rbegin(); it != rev.rend(); ++it) {
-                const std::string& pl = f.node_label_str[*it];                 // Strain::plain_seq, Strain.cpp:211-223
-                if (pl != "^" && pl != "$" && pl != "-" && pl != "=") q += pl;
-            }
-            job.seqs.push_back(q);
+            job.seqs.push_back(path_seq(s, true));
             job.abund.push_back((double)s.abundance);
         }
     }
-    if (level_log) fclose(level_log);
-    for (size_t k = 0; k + 1 < ev_used; k += 2) {
-        float ms = 0;
-        HIPCHK(hipEventSynchronize(ev_pool[k + 1]));
-        HIPCHK(hipEventElapsedTime(&ms, ev_pool[k], ev_pool[k + 1]));
-        sampler_ms += ms;
+    // The walk's figures into job.stats (the counters of every level are there already); the event pairs of the timed levels
+    // are read now, after the walk.
+    void report() {
+        for (size_t k = 0; k + 1 < w.ev_used; k += 2) {
+            float ms = 0;
+            HIPCHK(hipEventSynchronize(w.ev_pool[k + 1]));
+            HIPCHK(hipEventElapsedTime(&ms, w.ev_pool[k], w.ev_pool[k + 1]));
+            job.stats.sampler_kernel_ms += ms;
+        }
+        w.ev_used = 0;
+        for (int k = 0; k < 3; k++) job.stats.host_us[k] = 1e3 * host_acc[k];
+        for (int k = 0; k < 2; k++) { job.stats.wake_us[k] = 1e3 * w.wake_acc[k]; w.wake_acc[k] = 0; }
     }
-    ev_used = 0;
-    for (int k = 0; k < 3; k++) job.stats.host_us[k] = 1e3 * host_acc[k];
-    for (int k = 0; k < 2; k++) { job.stats.wake_us[k] = 1e3 * wake_acc[k]; wake_acc[k] = 0; }
-    job.stats.sampler_kernel_ms = sampler_ms;
-    job.stats.sampler_launches = sampler_launches;
-    job.stats.sampler_read_copies = sampler_copies;
-    job.stats.level_launches = level_launches;
-    job.stats.draws = draws;
-    job.stats.exact_draws = exact;
-    job.stats.slow_draws = slow;
-    job.stats.chain_passes = passes;
-    job.stats.chain_cycles = (long)chain_cycles;
-    job.stats.chain_wall_ticks = (long)chain_wall;
-    job.stats.sampler_strains = sampler_strains;
-    job.stats.level_kernel_ticks = (long)level_ticks;
-    job.stats.sampler_level_ticks = (long)sampler_ticks;
+
+    int model_new() {
+        if (!free_models.empty()) { const int m = free_models.back(); free_models.pop_back(); return m; }
+        models.emplace_back();
+        return (int)models.size() - 1;
+    }
+    void drop(const HStrain& s) { free_slots.push_back(s.slot); free_models.push_back(s.model); }
+    void lap(int k) { const double t = now_ms(); host_acc[k] += t - t_mark; t_mark = t; }
+    // the labels along the strain's path, root first: all of them (strain_seq), or without ^ $ - = (Strain::plain_seq,
+    // Strain.cpp:211-223)
+    std::string path_seq(const HStrain& s, bool plain) const {
+        std::vector<int> rev;
+        for (int t = s.tail; t >= 0; t = arena[t].parent) rev.push_back(arena[t].node);
+        std::string q;
+        for (auto it = rev.rbegin(); it != rev.rend(); ++it) {
+            const std::string& pl = f.node_label_str[*it];
+            if (!plain || (pl != "^" && pl != "$" && pl != "-" && pl != "=")) q += pl;
+        }
+        return q;
+    }
+    void trace_dump(const char* when, int level, const std::vector<HStrain>& sv) {
+        if (!want_trace || sv.empty()) return;
+        std::string& tr = job.trace;
+        tr += "------------------------------\n"; tr += when; tr += "\nlevel: "; tr += std::to_string(level); tr += "\n";
+        for (const auto& s : sv) { tr += path_seq(s, false); tr += "\t"; fmt_g17(tr, (double)s.abundance); tr += "\n"; }
+    }
+    static void sort_strains(std::vector<HStrain>& sv) {                 // std::sort, abundance descending
+        std::vector<int> perm(sv.size());
+        for (size_t i = 0; i < sv.size(); i++) perm[i] = (int)i;
+        std_sort_perm(perm, [&](int a, int b) { return sv[a].abundance > sv[b].abundance; });
+        std::vector<HStrain> t;
+        t.reserve(sv.size());
+        for (int i : perm) t.push_back(sv[i]);
+        sv.swap(t);
+    }
+    static ld seq_identity(const std::string& a, const std::string& b) {  // NonparametricClustering.cpp:584-612
+        int iden = 0, len = 0;
+        for (size_t i = 0; i < a.size(); ++i) {
+            const char x = a[i], y = i < b.size() ? b[i] : 0;
+            if (x == '-' && y == '-') continue;
+            else if (x == '=' && y == '=') continue;
+            else if (x == '=' && y == '-') continue;
+            else if (x == '-' && y == '=') continue;
+            else if (x == '^' && y == '^') continue;
+            else if (x == y) iden += 1;
+            len += 1;
+        }
+        return (ld)((iden + 0.0) / len);
+    }
+};
+
+void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
+    const int n_reads = (int)job.reads.size();
+    const double t_cluster0 = now_ms();
+
+    // ---- pseudo level holding every read once, for read_assign (NonparametricClustering.cpp:776-836)
+    const int final_e0 = (int)f.ent_rid.size();
+    long total_copies = 0;
+    {
+        int qo = 0;
+        for (int i = 0; i < n_reads; i++) {
+            f.ent_rid.push_back(i); f.ent_cn.push_back(job.reads[i].cn); f.ent_lab_off.push_back(0);
+            f.ent_lab_len.push_back(0); f.ent_first.push_back(1);
+            qo += job.reads[i].cn;
+        }
+        total_copies = qo;
+    }
+    // prefix of copy numbers inside each level
+    std::vector<int>& ent_qoff = ent_qoff_buf;                           // (the slot's: reused from region to region)
+    ent_qoff.assign(f.ent_rid.size(), 0);
+    int max_level_entries = n_reads, max_level_q = 0;
+    for (int l = 0; l < f.n_levels; l++) {
+        int qo = 0;
+        for (int x = f.level_ent_ptr[l]; x < f.level_ent_ptr[l + 1]; x++) { ent_qoff[x] = qo; qo += f.ent_cn[x]; }
+        max_level_entries = std::max(max_level_entries, f.level_ent_ptr[l + 1] - f.level_ent_ptr[l]);
+        max_level_q = std::max(max_level_q, qo);
+    }
+    { int qo = 0; for (int i = 0; i < n_reads; i++) { ent_qoff[final_e0 + i] = qo; qo += job.reads[i].cn; } }
+    const long qcap = std::max<long>(std::max<long>(max_level_q, total_copies), 1);
+    // cells of a read_loglik row that can hold a value when level l starts: the reads of the levels before it and their
+    // mates (the soft update enters a mate the first time it is asked for, Strain.cpp:147-150) -- a prefix of the read ids
+    std::vector<int> level_hi((size_t)f.n_levels + 1, 0);
+    for (int l = 0; l < f.n_levels; l++) {
+        int hi = level_hi[(size_t)l];
+        for (int x = f.level_ent_ptr[l]; x < f.level_ent_ptr[l + 1]; x++) {
+            const int rid = f.ent_rid[x];
+            hi = std::max(hi, rid + 1);
+            for (int k = job.mate_off[(size_t)rid]; k < job.mate_off[(size_t)rid + 1]; k++) hi = std::max(hi, job.mate_idx[(size_t)k] + 1);
+        }
+        level_hi[(size_t)l + 1] = hi;
+    }
+
+    // ---- upload the static arrays; the rows start empty, the uniforms are the context's
+    JobDev jd = job_dev(*stage, f, ent_qoff, job.mate_off, job.mate_idx, n_reads, qcap, max_level_entries);
+    jd.ll = (double*)b_ll.ensure(sizeof(double) * (size_t)jd.ll_stride * MAXS);
+    jd.has = (uint8_t*)b_has.ensure((size_t)n_reads + 8);
+    HIPCHK(hipMemsetAsync(jd.has, 0, (size_t)n_reads + 8, st));
+    jd.U = ctx->dU;
+    jd.Uf = ctx->dUf;
+    // the batched level kernels find the region through a pointer: the block travels once, with the uploads
+    const JobDev* jd_dev = (const JobDev*)b_jobdev.ensure(sizeof(JobDev));
+    stage->h2d((void*)jd_dev, &jd, sizeof jd, st);
+
+    // ---- a16: every edge support on the device
+    {
+        std::vector<int> esrc(f.out_node.size());
+        for (int a = 0; a < f.n_nodes; a++) for (int x = f.out_ptr[a]; x < f.out_ptr[a + 1]; x++) esrc[x] = a;
+        int* d_out_ptr = upload(*stage, b_out_ptr, f.out_ptr, st);
+        int* d_out_node = upload(*stage, b_out_node, f.out_node, st);
+        int* d_pool_ptr = upload(*stage, b_pool_ptr, f.pool_ptr, st);
+        int* d_pool_rid = upload(*stage, b_pool_rid, f.pool_rid, st);
+        int* d_pool_cn = upload(*stage, b_pool_cn, f.pool_cn, st);
+        uint8_t* d_isend = upload(*stage, b_isend, f.node_is_end, st);
+        int* d_esrc = upload(*stage, b_esrc, esrc, st);
+        int* d_sup = (int*)b_support.ensure(sizeof(int) * std::max<size_t>(esrc.size(), 1));
+        launch_edge_support(st, d_out_ptr, d_out_node, d_pool_ptr, d_pool_rid, d_pool_cn, d_isend, d_esrc, (int)esrc.size(),
+                            f.pools_sorted ? 1 : 0, d_sup);
+        if (!esrc.empty())
+            stage->d2h(f.out_support.data(), d_sup, sizeof(int) * esrc.size(), st);
+        const double t_sync0 = now_ms();
+        sync_stream();
+        stage->land();
+        if (stage != &passthrough) ctx->release_arena(stage);      // every transfer of the set-up is done
+        stage = &passthrough;
+        if (getenv("SC_SYNC_LOG")) fprintf(stderr, "sync uploads+edge_support %.3f ms (since cluster start %.3f)\n", now_ms() - t_sync0, now_ms() - t_cluster0);
+        job.edge_support = f.out_support;
+    }
+
+    // ---- level walk: from here on the region's host work is a few microseconds per level
+    if (setup_held) { ctx->setup_leave(); setup_held = false; }
+    job.stats.setup_ms = now_ms() - t_cluster0;
+    MailHold mail_hold{this};          // the mailbox the region walks on (resident workers)
+    if (ctx->resident) {
+        const double t_m0 = now_ms();
+        mslot.store(ctx->acquire_mailbox(this), std::memory_order_release);
+        job.stats.mailbox_ms = now_ms() - t_m0;
+        __atomic_store_n(&Rh->seq, 0u, __ATOMIC_RELEASE);       // (stamps are the mailbox's from here on: never 0)
+    }
+    LevelWalk(*this, job, f, jd, jd_dev, level_hi, final_e0, total_copies, mail_hold).run();
 }
 
 void Worker::process(Job& job) {
@@ -1950,12 +2013,7 @@ void sc_ctx_destroy(sc_ctx* h) {
     if (ctx->rstream) (void)hipStreamDestroy(ctx->rstream);
     if (ctx->mail_h) (void)hipHostFree(ctx->mail_h);
     if (ctx->ctl_h) (void)hipHostFree(ctx->ctl_h);
-    for (auto& w : ctx->workers) {
-        for (hipEvent_t e : w->ev_pool) (void)hipEventDestroy(e);
-        if (w->sync_ev) (void)hipEventDestroy(w->sync_ev);
-        if (w->st && w->own_stream) (void)hipStreamDestroy(w->st);
-    }
-    ctx->workers.clear();
+    ctx->workers.clear();                      // (before P_all / R_all / Pd_all: the slots' blocks are the context's)
     if (ctx->P_all) (void)hipHostFree(ctx->P_all);
     if (ctx->R_all) (void)hipHostFree(ctx->R_all);
     if (ctx->Pd_all) (void)hipFree(ctx->Pd_all);
@@ -2142,45 +2200,29 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
     if (nm > 0 && !mate_idx) return SC_ERR_ARG;
     for (int i = 0; i < nm; i++) if (mate_idx[i] < -1 || mate_idx[i] >= n_reads) return SC_ERR_ARG;
     try {
-        HIPCHK(hipSetDevice(ctx->device));
         Worker w;                                      // a private worker: own stream, own parameter / result blocks
-        w.ctx = ctx;
-        w.init();
-        w.stage = &w.passthrough;
-        w.passthrough.on = false;
-        struct Free {
-            Worker& w;
-            ~Free() { (void)hipHostFree(w.Ph); (void)hipFree(w.Pd); (void)hipHostFree(w.Rh); (void)hipEventDestroy(w.sync_ev); (void)hipStreamDestroy(w.st); }
-        } free_w{w};
+        w.init_private(ctx);
         // entries [0, e0) belong to other levels: they name other reads (the last ones, backwards), so that an entry index
         // that misses e0 reads the wrong row
         const int E = e0 + n_ent;
-        std::vector<int> rid((size_t)E), cn((size_t)E, 1), lab_off((size_t)E), lab_len((size_t)E, 1), qoff((size_t)E, 0);
-        std::vector<uint8_t> first((size_t)E, 1), labels((size_t)E + 1);
-        labels[(size_t)E] = 0;                         // the strains' node label (read only by the update, which does not run)
+        FlatGraph f;
+        f.K = KMAX; f.code_N = KMAX;
+        f.ent_rid.resize((size_t)E); f.ent_cn.assign((size_t)E, 1); f.ent_lab_off.resize((size_t)E); f.ent_lab_len.assign((size_t)E, 1);
+        f.ent_first.assign((size_t)E, 1);
+        f.labels.assign((size_t)E + 1, 0);             // [E]: the strains' node label (read only by the update, which does not run)
+        std::vector<int> qoff((size_t)E, 0);
         for (int e = 0; e < E; e++) {
             const int r = e - e0;
-            rid[(size_t)e] = r >= 0 ? ent_rid[r] : n_reads - 1 - e % n_reads;
-            lab_off[(size_t)e] = e;
-            labels[(size_t)e] = (uint8_t)(r >= 0 ? ent_sym[r] : 0);
+            f.ent_rid[(size_t)e] = r >= 0 ? ent_rid[r] : n_reads - 1 - e % n_reads;
+            f.ent_lab_off[(size_t)e] = e;
+            f.labels[(size_t)e] = (uint8_t)(r >= 0 ? ent_sym[r] : 0);
         }
-        for (int r = 0, q = 0; r < n_ent; r++) { cn[(size_t)(e0 + r)] = ent_cn[r]; qoff[(size_t)(e0 + r)] = q; q += ent_cn[r]; }
+        for (int r = 0, q = 0; r < n_ent; r++) { f.ent_cn[(size_t)(e0 + r)] = ent_cn[r]; qoff[(size_t)(e0 + r)] = q; q += ent_cn[r]; }
         const hipStream_t st = w.st;
-        JobDev jd{};
-        jd.ent_rid = upload(w.passthrough, w.b_ent_rid, rid, st);
-        jd.ent_cn = upload(w.passthrough, w.b_ent_cn, cn, st);
-        jd.ent_lab_off = upload(w.passthrough, w.b_ent_lab_off, lab_off, st);
-        jd.ent_lab_len = upload(w.passthrough, w.b_ent_lab_len, lab_len, st);
-        jd.ent_first = upload(w.passthrough, w.b_ent_first, first, st);
-        jd.ent_qoff = upload(w.passthrough, w.b_ent_qoff, qoff, st);
-        jd.labels = upload(w.passthrough, w.b_labels, labels, st);
         const std::vector<int> mptr(mate_off, mate_off + n_reads + 1), midx(mate_idx, mate_idx + nm);      // (alive until the copies are done)
-        jd.mate_ptr = upload(w.passthrough, w.b_mate_ptr, mptr, st);
-        jd.mate_idx = upload(w.passthrough, w.b_mate_idx, midx, st);
-        jd.n_reads = n_reads; jd.K = KMAX; jd.code_N = KMAX;
+        JobDev jd = w.job_dev(w.passthrough, f, qoff, mptr, midx, n_reads, std::max<long>(Q, 1), n_ent);
         // rows as in the region set-up; strain s lives in row slot(s), not in row s
         auto slot = [](int s) { return (s * 37 + 5) % MAXS; };
-        jd.ll_stride = ((long)n_reads + 3) & ~3L;
         std::vector<double> rows((size_t)jd.ll_stride * MAXS, 0.0);
         for (int s = 0; s < S; s++) std::memcpy(&rows[(size_t)slot(s) * jd.ll_stride], ll + (size_t)s * n_reads, sizeof(double) * n_reads);
         jd.ll = upload(w.passthrough, w.b_ll, rows, st);
@@ -2194,14 +2236,6 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         DevBuf b_u, b_uf;
         jd.U = upload(w.passthrough, b_u, u, st);
         jd.Uf = upload(w.passthrough, b_uf, uf, st);
-        const long qcap = std::max<long>(Q, 1);
-        jd.isnew = (uint8_t*)w.b_isnew.ensure((size_t)n_ent + 8);
-        jd.qcap = qcap;
-        jd.tabA = (double*)w.b_tabA.ensure(sizeof(double) * (size_t)qcap * MAXS);
-        jd.tabLf = (float*)w.b_tabLf.ensure(sizeof(float) * (size_t)(std::min<long>(qcap, MAX_DRAWS) + 4) * 136);
-        jd.qcode = (uint8_t*)w.b_qcode.ensure((size_t)qcap + 8);
-        jd.qent = (int*)w.b_qent.ensure(sizeof(int) * (size_t)qcap);
-        jd.quid = (int*)w.b_quid.ensure(sizeof(int) * (size_t)qcap);
         const JobDev* jd_dev = (const JobDev*)w.b_jobdev.ensure(sizeof(JobDev));
         HIPCHK(hipMemcpyAsync((void*)jd_dev, &jd, sizeof jd, hipMemcpyHostToDevice, st));
 
@@ -2211,9 +2245,9 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         H.mode = MODE_SAMPLE; H.S = S; H.e0 = e0; H.e1 = E; H.Q = (int)Q; H.n_sweeps = n_sweeps;
         H.n_copy = 0; H.do_update = 0; H.seq = 1;
         std::memset(w.Rh, 0, sizeof(LevelResult));
-        const int kind = level_kind(H);
         LevelBatch batch;
-        batch.it[0] = LevelItem{jd_dev, H, kind | (level_lds_kb(H, KMAX) << 8), w.Pm, w.Rd};
+        batch.it[0] = w.level_item(jd_dev, H, KMAX);
+        const int kind = batch.it[0].kind & 0xFF;
         launch_level_batch(st, kind, batch, 1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
@@ -2240,12 +2274,8 @@ int sc_msa_align(sc_ctx* h, const char* seq_text, const int* seq_off, int n, cha
     Ctx* ctx = &h->c;
     // runs on a private worker object (own stream) so it can be called while regions are in flight
     try {
-        HIPCHK(hipSetDevice(ctx->device));
         Worker w;
-        w.ctx = ctx;
-        w.init();
-        w.stage = &w.passthrough;
-        w.passthrough.on = false;
+        w.init_private(ctx);
         std::vector<std::string> seqs((size_t)n), rows;
         for (int i = 0; i < n; i++) seqs[i].assign(seq_text + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
         int ncol;
@@ -2255,9 +2285,6 @@ int sc_msa_align(sc_ctx* h, const char* seq_text, const int* seq_off, int n, cha
         int rc = SC_OK;
         if (!rows_out || (long)n * (ncol + 1) > cap) rc = SC_ERR_CAPACITY;
         else for (int i = 0; i < n; i++) { std::memcpy(rows_out + (long)i * (ncol + 1), rows[i].data(), (size_t)ncol); rows_out[(long)i * (ncol + 1) + ncol] = 0; }
-        (void)hipHostFree(w.Ph); (void)hipFree(w.Pd); (void)hipHostFree(w.Rh);
-        (void)hipEventDestroy(w.sync_ev);
-        (void)hipStreamDestroy(w.st);
         return rc;
     } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
     catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
