@@ -191,6 +191,11 @@ const char* sc_aln_error(sc_aln* aln);
 long sc_aln_records(sc_aln* aln);
 /* alignments of one reference and the reference bases they cover: what a scheduler needs to price a region */
 int sc_aln_ref_stats(sc_aln* aln, const char* gene, long* n_records, long* aligned_bases);
+/* Every record of the file in file order, whatever its reference (the reads stage 4 extracts, extract_reads.py:46-112):
+ * records [first, first + n) as lines "QNAME\tFLAG\tSEQ\tQUAL\n" (SAM columns 1, 2, 10, 11, as the file holds them) into
+ * buf.  Stops early at a record that does not fit: *n_out records, *len_out bytes (SC_ERR_CAPACITY when not even the first
+ * fits).  Needs a handle that kept all records (sc_aln_open). */
+int sc_aln_walk(sc_aln* aln, long first, long n, char* buf, long cap, long* n_out, long* len_out);
 
 /* What window_adjust reads out of the pileup of gene:P-Q (StrainCall.cpp:702-736): for position P+i, whether any
  * read covers it, and whether column 5 of its pileup line would hold a '+' (insertion) / a '-' or '*' (deletion) --
@@ -235,6 +240,35 @@ int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const
 int sc_depth_scan_runs(int device, const int* ref_len, int n_refs, const int* run_ref, const int* run_start, const int* run_end,
                        long n_runs, int max_gap, int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap,
                        int* n_intervals, sc_depth_stats* stats);
+
+/* ---- rambl.py stage 4 on the device (rambl_amd/csrc/sc_align.hip) --------------------------------------------
+ *
+ * scripts/recluster_data_to_seed_otus.py:198-277 extracts the reads the gene-database BAMs mapped,
+ * aligns them again with `bowtie2 --sensitive-local` to the seed OTUs and keeps what `samtools view -F1804` keeps.
+ * sc_align_reads computes the exact optimum of bowtie2's --local scoring instead (match +2, mismatch -(2 + floor(4 *
+ * min(Q,40) / 40)), a base outside ACGT -1, a gap of n -(5 + 3n), no gap within 4 rows of either read end), every seed on
+ * both strands, ties to the lower seed index, then the forward strand, then the smaller end column on the seed, then the
+ * smaller end row; traceback diagonal before D before I, extension before opening.
+ *   seed_text/seed_off[n_seeds+1]     the seeds back to back (1..8192 bases each)
+ *   read_text/qual_text/read_off[n+1] the reads as they were sequenced (1..512 bases each; QUAL Phred+33, NULL: Q40)
+ * Out, per read: as = best score (whether or not it is valid); xs = best valid score of any other (seed, strand), -1 when
+ * none; and where as >= 20 + 8 ln(length) (in double): seed (else -1), strand (1: the reverse complement of the read
+ * aligned), pos (1-based on the seed), nm, and n_cigar operations at cigar[read * cigar_stride] in BAM form (length << 4 |
+ * op; M 0, I 1, D 2, S 4).  cigar_stride >= longest read / 2 + 4 always suffices.  Reads or seeds outside the limits:
+ * SC_ERR_UNSUPPORTED; the message of the calling thread's last failure is in sc_align_error(). */
+typedef struct sc_align_stats {
+    double upload_ms;      /* HIP events: seeds and reads to the device */
+    double score_ms;       /* HIP events: k_sw_score, every (read, seed, strand) tile */
+    double trace_ms;       /* HIP events: k_sw_trace, one window per aligned read */
+    double total_ms;       /* wall time of the call, host packing included */
+    long score_cells;      /* DP cells of the score pass: sum of 2 * read length * total seed length */
+    long trace_cells;      /* DP cells the traceback pass swept (its column blocks recompute from the window start) */
+    long n_traced;         /* reads that aligned */
+} sc_align_stats;
+int sc_align_reads(int device, const char* seed_text, const long* seed_off, int n_seeds, const char* read_text, const char* qual_text,
+                   const long* read_off, int n_reads, int* as, int* xs, int* seed, int* strand, int* pos, int* nm, unsigned* cigar,
+                   int cigar_stride, int* n_cigar, sc_align_stats* stats);
+const char* sc_align_error(void);
 
 #ifdef __cplusplus
 }

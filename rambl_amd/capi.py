@@ -30,6 +30,14 @@ class ScStats(C.Structure):
         return {k: (list(getattr(self, k)) if k in ("xcd_levels", "kind_levels", "host_us", "wake_us") else getattr(self, k)) for k, _ in self._fields_}
 
 
+class ScAlignStats(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("score_ms", C.c_double), ("trace_ms", C.c_double), ("total_ms", C.c_double),
+                ("score_cells", C.c_long), ("trace_cells", C.c_long), ("n_traced", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StrainCallError(RuntimeError):
     def __init__(self, code, msg=""):
         super().__init__("%s (%d)%s" % (ERRORS.get(code, "error"), code, (": " + msg) if msg else ""))
@@ -83,7 +91,13 @@ def load_library():
     lib.sc_reads_get.argtypes = [vp, ip, pi, pc, pi, pc, pi, pi, pi, pi, C.POINTER(C.c_long), ip]
     lib.sc_reads_free.argtypes = [vp]
     lib.sc_reads_free.restype = None
-    for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get"):
+    lib.sc_aln_walk.argtypes = [vp, C.c_long, C.c_long, C.c_char_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    lp = C.POINTER(C.c_long)
+    lib.sc_align_reads.argtypes = [C.c_int, cp, lp, C.c_int, cp, cp, lp, C.c_int, ip, ip, ip, ip, ip, ip, up, C.c_int, ip,
+                                   C.POINTER(ScAlignStats)]
+    lib.sc_align_error.argtypes = []
+    lib.sc_align_error.restype = cp
+    for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
               "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level"):
@@ -94,7 +108,8 @@ def load_library():
 EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "sc_host_plan", "sc_host_bind", "sc_roi_submit", "sc_roi_wait", "sc_roi_result",
            "sc_roi_graph_dump", "sc_roi_trace", "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align",
            "sc_roi_thread_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
-           "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs"]
+           "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
+           "sc_align_error"]
 
 
 def default_params(error_rate=0.01, tau=0.02, diff_rate=0.01, graph_only=False, want_trace=False, want_timing=False, want_graph=False):
@@ -229,6 +244,24 @@ class NativeAln:
 
     def records(self):
         return lib().sc_aln_records(self._h)
+
+    def walk(self, chunk=1 << 24):
+        """(QNAME, FLAG, SEQ, QUAL) of every record in file order, whatever its reference (sc_aln_walk)."""
+        buf = C.create_string_buffer(chunk)
+        first, n_out, used = 0, C.c_long(), C.c_long()
+        while True:
+            rc = lib().sc_aln_walk(self._h, first, 1 << 20, buf, len(buf), C.byref(n_out), C.byref(used))
+            if rc == -5:
+                buf = C.create_string_buffer(len(buf) * 4)
+                continue
+            if rc != SC_OK:
+                raise StrainCallError(rc, self.path)
+            if n_out.value == 0:
+                return
+            for line in buf.raw[:used.value].split(b"\n")[:-1]:
+                q, f, seq, qual = line.split(b"\t")
+                yield q, int(f), seq, qual
+            first += n_out.value
 
     def ref_stats(self, gene):
         """(alignments of the reference, reference bases they cover)."""
@@ -435,3 +468,38 @@ class Context:
             raise self._err(rc)
         w = ncol.value + 1
         return [out.raw[i * w:i * w + ncol.value].decode("ascii") for i in range(len(seqs))]
+
+
+class AlignResult:
+    """Per read: as_ (best score), xs (-1: none), seed (-1: no valid alignment), strand, pos (1-based), nm, cigar (text)."""
+
+    def __init__(self, as_, xs, seed, strand, pos, nm, cigar, stats):
+        self.as_, self.xs, self.seed, self.strand, self.pos, self.nm, self.cigar, self.stats = as_, xs, seed, strand, pos, nm, cigar, stats
+
+
+def align_reads(seeds, reads, quals=None, device=0):
+    """sc_align_reads: every read against every seed on both strands (stage 4).  seeds, reads, quals:
+    lists of bytes (quals None, or an entry b"*": Q40)."""
+    import numpy as np
+    n = len(reads)
+    sl = np.array([0] + [len(x) for x in seeds], dtype=np.int64).cumsum()
+    rl = np.array([0] + [len(x) for x in reads], dtype=np.int64).cumsum()
+    qtext = None
+    if quals is not None:
+        qtext = b"".join(q if (q != b"*" and len(q) == len(r)) else b"I" * len(r) for r, q in zip(reads, quals))
+    stride = max([len(x) for x in reads] + [0]) // 2 + 4
+    as_, xs, seed, strand, pos, nm, ncig = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(7))
+    cig = np.zeros(max(n, 1) * stride, dtype=np.uint32)
+    st = ScAlignStats()
+    ip, lp, up = C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_uint)
+    rc = lib().sc_align_reads(device, b"".join(seeds), sl.ctypes.data_as(lp), len(seeds), b"".join(reads), qtext, rl.ctypes.data_as(lp), n,
+                              as_.ctypes.data_as(ip), xs.ctypes.data_as(ip), seed.ctypes.data_as(ip), strand.ctypes.data_as(ip),
+                              pos.ctypes.data_as(ip), nm.ctypes.data_as(ip), cig.ctypes.data_as(up), stride, ncig.ctypes.data_as(ip),
+                              C.byref(st))
+    if rc != SC_OK:
+        raise StrainCallError(rc, lib().sc_align_error().decode())
+    cigars = []
+    for r in range(n):
+        ops = cig[r * stride:r * stride + ncig[r]]
+        cigars.append("".join("%d%s" % (int(v) >> 4, "MIDNSHP=X"[int(v) & 15]) for v in ops) if ncig[r] else "*")
+    return AlignResult(as_[:n], xs[:n], seed[:n], strand[:n], pos[:n], nm[:n], cigars, st)

@@ -143,7 +143,8 @@ bool parse_sam_part(const sc_aln& a, const char* p, const char* end, SamPart& ou
                 if (!ok) { out.error = "SAM record with a non-numeric FLAG, POS or MAPQ"; return false; }
                 r.cigar = f[5]; r.clen = (int)(fend(5) - f[5]);
                 r.seq = f[9]; r.slen = (int)(fend(9) - f[9]);
-                r.quallen = (int)(qual_end - f[10]);
+                r.qual = f[10]; r.quallen = (int)(qual_end - f[10]);
+                r.ord = (long)(p - (const char*)a.map);
                 r.ref_end = ref_span_end(r.pos, r.cigar, r.clen);
                 const size_t rl = (size_t)(fend(2) - f[2]);
                 if (!stat || last_name.size() != rl || memcmp(last_name.data(), f[2], rl) != 0) {
@@ -334,6 +335,11 @@ bool load_bam(sc_aln& a, const unsigned char* src, size_t n) {
         r.seq = sq; r.slen = std::max(l_seq, 1);
         p += (size_t)(l_seq + 1) / 2;
         r.quallen = (l_seq == 0 || d[p] == 0xff) ? 1 : l_seq;            // "*" when absent
+        char* ql = a.alloc((size_t)r.quallen + 1);
+        if (r.quallen == 1 && (l_seq == 0 || d[p] == 0xff)) ql[0] = '*';
+        else for (int k = 0; k < l_seq; k++) ql[k] = (char)(d[p + (size_t)k] + 33);
+        r.qual = ql;
+        r.ord = (long)o;
         r.flag = (int)flag; r.pos = pos + 1; r.mapq = (int)mapq;
         r.ref_end = ref_span_end(r.pos, r.cigar, r.clen);
         a.by_ref[rname].push_back(r);
@@ -513,6 +519,32 @@ int sc_aln_ref_stats(sc_aln* a, const char* gene, long* n_records, long* aligned
     if (n_records) *n_records = n;
     if (aligned_bases) *aligned_bases = b;
     return SC_OK;
+}
+
+int sc_aln_walk(sc_aln* a, long first, long n, char* buf, long cap, long* n_out, long* len_out) {
+    if (!a || first < 0 || n < 0 || (n > 0 && !buf) || !n_out || !len_out) return SC_ERR_ARG;
+    std::call_once(a->order_once, [a] {
+        a->order.reserve((size_t)a->n_records);
+        for (auto& kv : a->by_ref) for (const Rec& r : kv.second) a->order.push_back(&r);
+        std::sort(a->order.begin(), a->order.end(), [](const Rec* x, const Rec* y) { return x->ord < y->ord; });
+    });
+    *n_out = 0; *len_out = 0;
+    long used = 0, k = 0;
+    for (; k < n && first + k < (long)a->order.size(); k++) {
+        const Rec& r = *a->order[(size_t)(first + k)];
+        char num[16];
+        const int nl = snprintf(num, sizeof num, "%d", r.flag);
+        const long need = (long)r.qlen + nl + r.slen + r.quallen + 4;
+        if (used + need > cap) break;
+        char* o = buf + used;
+        memcpy(o, r.qname, (size_t)r.qlen); o += r.qlen; *o++ = '\t';
+        memcpy(o, num, (size_t)nl); o += nl; *o++ = '\t';
+        memcpy(o, r.seq, (size_t)r.slen); o += r.slen; *o++ = '\t';
+        memcpy(o, r.qual, (size_t)r.quallen); o += r.quallen; *o++ = '\n';
+        used += need;
+    }
+    *n_out = k; *len_out = used;
+    return (k == 0 && n > 0 && first < (long)a->order.size()) ? SC_ERR_CAPACITY : SC_OK;
 }
 
 int sc_aln_pileup_flags(sc_aln* a, const char* gene, int P, int Q, int mq, unsigned char* covered, unsigned char* has_ins,

@@ -4,17 +4,19 @@
 
 #include <algorithm>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
 namespace sc_ingest {
-struct Rec {                       // the SAM fields the path reads: 1 2 4 5 6 10 (+ the length of 11)
-    const char* qname; const char* cigar; const char* seq;
+struct Rec {                       // the SAM fields the path reads: 1 2 4 5 6 10 11
+    const char* qname; const char* cigar; const char* seq; const char* qual;
     int qlen, clen, slen, quallen;
     int flag, pos, mapq;
     int ref_end;                   // last reference position covered, ops M D N = X (what `view` and `mpileup` overlap on)
+    long ord;                      // where the record starts in the (inflated) file: file order across references
 };
 }  // namespace sc_ingest
 
@@ -31,6 +33,8 @@ struct sc_aln {
     std::unordered_map<std::string, RefStat> stats;
     bool keep_all = true;
     std::unordered_set<std::string> keep;                                     // references whose records are kept when !keep_all
+    std::once_flag order_once;
+    std::vector<const sc_ingest::Rec*> order;                                 // every kept record in file order (sc_aln_walk)
     bool wants(const char* name, size_t n) const { return keep_all || keep.count(std::string(name, n)) != 0; }
 
     char* alloc(size_t n) {
