@@ -147,9 +147,11 @@ def sam_header(seed_names, seed_seqs):
     return "@HD\tVN:1.0\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(seed_names, seed_seqs))
 
 
-def recluster(gene_fasta, seed_file, bam_file, out_dir=".", mapper=MAPPER, map_args=MAP_ARGS, device=0, verbose=False):
+def recluster(gene_fasta, seed_file, bam_file, out_dir=".", mapper=MAPPER, map_args=MAP_ARGS, device=0, verbose=False, alns=None):
     """recluster_data (:198-277).  Writes <out_dir>/0_otu_dir/seed_otus.fasta(.fai) and <out_dir>/to_seed_otus.all.sam;
-    returns the SAM path and the sc_align_stats of the device call."""
+    returns the SAM path and the sc_align_stats of the device call.  `alns`: the files of `bam_file` already opened
+    (capi.NativeAln, in list order; the caller keeps and closes them) -- the whole-pipeline driver reads them once for
+    stages 1 and 4."""
     if mapper != MAPPER or map_args != MAP_ARGS:
         raise ValueError("stage 4 computes bowtie2 %s alignments on the GPU; mapper %r with arguments %r is not available "
                          "(only -m %s -A %s)" % (MAP_ARGS, mapper, map_args, MAPPER, MAP_ARGS))
@@ -159,6 +161,11 @@ def recluster(gene_fasta, seed_file, bam_file, out_dir=".", mapper=MAPPER, map_a
     seed_seqs = write_seed_fasta(gene_fasta, seeds, os.path.join(otu_dir, "seed_otus.fasta"))
 
     def records():
+        if alns is not None:
+            for aln in alns:
+                for r in aln.walk():
+                    yield r
+            return
         for path in read_bam_list(bam_file):
             aln = capi.NativeAln(path)
             try:
