@@ -59,7 +59,7 @@ struct ThreadTables {
     std::vector<int> off;             // [glen*8+1] pool offsets
     std::vector<int> pool;            // read ids of every class, ascending
 };
-// Produces the tables for one region (the device implementation lives in sc_api.cpp).
+// Produces the tables for one region (the device implementation lives in sc_region.cpp).
 using ThreadFn = std::function<void(const std::string& G, const std::vector<struct AlignedRead>& R,
                                     const std::vector<std::vector<CigarOp>>& cigars, ThreadTables& out)>;
 

@@ -1,0 +1,118 @@
+// Host-side plumbing of libstraincall_hip.so: the errors its code throws, and the HIP resources it owns by scope.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace sc {
+
+struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct ScError : std::runtime_error {
+    int code;
+    ScError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
+};
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw HipError(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+inline double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// growable device buffer
+// A device buffer that only grows.  While regions are in flight nothing is handed back to the driver (hipFree waits for
+// the device): an outgrown buffer is kept until the worker goes; growth is geometric, so that is at most as much again --
+// nothing next to 288 GB.  (Measured: no difference to freeing at once; the stalls under load came from pageable copies,
+// see PinnedArena.  SC_DEVBUF_KEEP=0 restores the old behaviour: `keep`, for the whole process, set by the contexts.)
+struct DevBuf {
+    static inline bool keep = true;
+    void* p = nullptr; size_t cap = 0;
+    std::vector<void*> outgrown;
+    void* ensure(size_t n) {
+        if (n > cap) {
+            if (p) { if (keep) outgrown.push_back(p); else (void)hipFree(p); }
+            size_t want = keep ? std::max<size_t>(n + n / 2 + 4096, 2 * cap) : n + n / 4 + 256;
+            HIPCHK(hipMalloc(&p, want));
+            cap = want;
+        }
+        return p;
+    }
+    ~DevBuf() { if (p) (void)hipFree(p); for (void* q : outgrown) (void)hipFree(q); }
+};
+// Pinned staging for a region's transfers.  A copy between the device and ordinary (pageable) host memory makes the
+// runtime pin those pages for the copy and let them go afterwards; with regions in flight that costs far more than the
+// copy -- registering and releasing user pages suspends every queue of the process (level kernels of ALL regions lasting
+// ~30 ms at once, a few times per region).  So every sizeable transfer goes through page-locked memory the worker owns:
+// grow-only chunks, handed out by a bump pointer, reused by the next region.
+struct PinnedArena {
+    struct Chunk { char* p; size_t cap, used; };
+    struct Back { void* dst; const void* src; size_t n; };      // device-to-host copies still to be moved to their vectors
+    std::vector<Chunk> chunks;
+    std::vector<Back> back;
+    bool on = true;                   // false: pass the copies through (a single region in flight suspends nobody)
+    void* take(size_t n) {
+        n = (n + 255) & ~(size_t)255;
+        for (Chunk& c : chunks) if (c.cap - c.used >= n) { void* r = c.p + c.used; c.used += n; return r; }
+        size_t cap = std::max<size_t>(n, (size_t)8 << 20);
+        if (!chunks.empty()) cap = std::max(cap, 2 * chunks.back().cap);
+        char* q = nullptr;
+        HIPCHK(hipHostMalloc((void**)&q, cap, hipHostMallocDefault));
+        chunks.push_back(Chunk{q, cap, n});
+        return q;
+    }
+    void reset() { for (Chunk& c : chunks) c.used = 0; back.clear(); }
+    void h2d(void* dst, const void* src, size_t n, hipStream_t st) {
+        if (n == 0) return;
+        if (!on) { HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st)); return; }
+        void* q = take(n);
+        memcpy(q, src, n);
+        HIPCHK(hipMemcpyAsync(dst, q, n, hipMemcpyHostToDevice, st));
+    }
+    void d2h(void* dst, const void* src, size_t n, hipStream_t st) {          // complete after the stream's synchronisation + land()
+        if (n == 0) return;
+        if (!on) { HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st)); return; }
+        void* q = take(n);
+        HIPCHK(hipMemcpyAsync(q, src, n, hipMemcpyDeviceToHost, st));
+        back.push_back(Back{dst, q, n});
+    }
+    void land() { for (const Back& b : back) memcpy(b.dst, b.src, b.n); back.clear(); }
+    ~PinnedArena() { for (Chunk& c : chunks) (void)hipHostFree(c.p); }
+};
+template <class T> T* upload(PinnedArena& ar, DevBuf& b, const std::vector<T>& v, hipStream_t st) {
+    T* d = (T*)b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
+    ar.h2d(d, v.data(), v.size() * sizeof(T), st);
+    return d;
+}
+
+// Owned HIP resources of a context: acquired by the constructor (HipError when that fails), released by the destructor.
+struct Stream {
+    hipStream_t st = nullptr;
+    Stream() { HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
+    explicit Stream(int priority) { HIPCHK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, priority)); }
+    Stream(Stream&& o) noexcept : st(o.st) { o.st = nullptr; }
+    Stream(const Stream&) = delete;
+    ~Stream() { if (st) (void)hipStreamDestroy(st); }
+};
+template <class T> struct HostMapped {                    // host memory the device reads and writes over PCIe: p there is d
+    T* p = nullptr; T* d = nullptr;
+    explicit HostMapped(size_t n) {
+        HIPCHK(hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent));
+        if (hipHostGetDevicePointer((void**)&d, p, 0) != hipSuccess) { (void)hipHostFree(p); throw HipError("hipHostGetDevicePointer"); }
+    }
+    HostMapped(const HostMapped&) = delete;
+    ~HostMapped() { (void)hipHostFree(p); }
+};
+template <class T> struct DevMem {
+    T* p = nullptr;
+    explicit DevMem(size_t n) { HIPCHK(hipMalloc((void**)&p, n * sizeof(T))); }
+    DevMem(const std::vector<T>& v) : DevMem(v.size()) {
+        if (hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); throw HipError("hipMemcpy"); }
+    }
+    DevMem(const DevMem&) = delete;
+    ~DevMem() { (void)hipFree(p); }
+};
+
+}  // namespace sc

@@ -1658,7 +1658,7 @@ __global__ __launch_bounds__(1024) void k_thread_sort_big(const int* __restrict_
 }
 
 // --------------------------------------------------------------------------
-// host-callable launchers (called from sc_api.cpp)
+// host-callable launchers (declared in sc_ctx.hpp; called from sc_sched.cpp, sc_region.cpp, sc_walk.cpp, sc_api.cpp)
 void launch_edge_support(hipStream_t st, const int* out_ptr, const int* out_node, const int* pool_ptr, const int* pool_rid,
                          const int* pool_cn, const uint8_t* node_is_end, const int* edge_src, int n_edges, int sorted,
                          int* support) {

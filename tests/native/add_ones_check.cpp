@@ -1,4 +1,4 @@
-// CPU check of sc_add_ones (rambl_amd/csrc/sc_api.cpp): k additions of 1 in x87 long double, bit for bit equal to
+// CPU check of sc_add_ones (rambl_amd/csrc/sc_walk.cpp): k additions of 1 in x87 long double, bit for bit equal to
 // the literal loop of the reference (NonparametricClustering.cpp:195), on values around binade borders and at random.
 #include <cmath>
 #include <cstdio>
