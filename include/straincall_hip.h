@@ -270,6 +270,41 @@ int sc_align_reads(int device, const char* seed_text, const long* seed_off, int 
                    int cigar_stride, int* n_cigar, sc_align_stats* stats);
 const char* sc_align_error(void);
 
+/* ---- the per-sample gene profile on the device (rambl_amd/csrc/sc_profile.hip) ---------------------------------
+ *
+ * scripts/per_sample_gene_profile_fast.py:80-153 searches a sample's read segments in the assembled genes with
+ * makeblastdb and `blastn -reward 1 -penalty -2` and turns the XML into a CSV with bigBlastParser and sqlite3.
+ * sc_profile_hits computes, for every (segment, gene), the exact optimum of that scoring instead (match +1, mismatch and
+ * any base outside ACGT -2, a gap of n bases -2.5 n, local), the better of the two strands (ties: forward, then the
+ * smaller end column on the gene, then the smaller end row), the alignment traced back from that cell diagonal before
+ * gap-in-segment before gap-in-gene, and E = ka_k * m * n * exp(-ka_lambda * S) with m the segment length and n the sum of
+ * the gene lengths.  No word-size seeding, no effective-length correction, no cap on targets.
+ *   gene_text/gene_off[n_genes+1]   the genes back to back (1..8192 bases each)
+ *   seg_text/seg_off[n_segs+1]      the segments as stored (1..512 bases each)
+ * Out: the hits with 100 * identity / align_len >= min_identity_pct and E <= max_evalue, sorted by (segment, gene):
+ * strand (1: the reverse complement of the segment aligned), raw score (may be x.5), identity (columns with equal ACGT
+ * bases), align_len (columns), query from/to (1-based on the segment as given), hit from/to (1-based on the gene; from > to
+ * on the reverse strand, as blastn prints it), E.  More than `cap` hits: SC_ERR_CAPACITY with *n_hits set to a capacity
+ * that suffices.  Lengths outside the limits: SC_ERR_UNSUPPORTED; the message of the calling thread's last failure is in
+ * sc_profile_error(). */
+typedef struct sc_profile_stats {
+    double upload_ms;      /* HIP events: genes and segments to the device */
+    double score_ms;       /* HIP events: k_bl_score, every (segment, gene, strand) tile */
+    double trace_ms;       /* HIP events: k_bl_trace, one window per (segment, gene) whose score passes the E-value */
+    double total_ms;       /* wall time of the call, host packing included */
+    long score_cells;      /* DP cells of the score pass: sum of 2 * segment length * total gene length */
+    long trace_cells;      /* DP cells the traceback pass swept */
+    long n_tiles;          /* (segment, gene, strand) tiles of the score pass */
+    long n_candidates;     /* tiles whose best score passes the E-value threshold */
+    long n_traced;         /* (segment, gene) pairs traced back */
+    long n_hits;           /* hits that pass both thresholds */
+} sc_profile_stats;
+int sc_profile_hits(int device, const char* gene_text, const long* gene_off, int n_genes, const char* seg_text, const long* seg_off,
+                    int n_segs, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, int* hit_seg, int* hit_gene,
+                    int* hit_strand, double* hit_score, int* identity, int* align_len, int* qfrom, int* qto, int* hfrom, int* hto,
+                    double* evalue, long cap, long* n_hits, sc_profile_stats* stats);
+const char* sc_profile_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,15 @@ class ScAlignStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScProfileStats(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("score_ms", C.c_double), ("trace_ms", C.c_double), ("total_ms", C.c_double),
+                ("score_cells", C.c_long), ("trace_cells", C.c_long), ("n_tiles", C.c_long), ("n_candidates", C.c_long),
+                ("n_traced", C.c_long), ("n_hits", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StrainCallError(RuntimeError):
     def __init__(self, code, msg=""):
         super().__init__("%s (%d)%s" % (ERRORS.get(code, "error"), code, (": " + msg) if msg else ""))
@@ -97,7 +106,11 @@ def load_library():
                                    C.POINTER(ScAlignStats)]
     lib.sc_align_error.argtypes = []
     lib.sc_align_error.restype = cp
-    for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads"):
+    lib.sc_profile_hits.argtypes = [C.c_int, cp, lp, C.c_int, cp, lp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, ip, ip, ip,
+                                    dp, ip, ip, ip, ip, ip, ip, dp, C.c_long, lp, C.POINTER(ScProfileStats)]
+    lib.sc_profile_error.argtypes = []
+    lib.sc_profile_error.restype = cp
+    for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads", "sc_profile_hits"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
               "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level"):
@@ -109,7 +122,7 @@ EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "
            "sc_roi_graph_dump", "sc_roi_trace", "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align",
            "sc_roi_thread_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
            "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
-           "sc_align_error"]
+           "sc_align_error", "sc_profile_hits", "sc_profile_error"]
 
 
 def default_params(error_rate=0.01, tau=0.02, diff_rate=0.01, graph_only=False, want_trace=False, want_timing=False, want_graph=False):
@@ -503,3 +516,62 @@ def align_reads(seeds, reads, quals=None, device=0):
         ops = cig[r * stride:r * stride + ncig[r]]
         cigars.append("".join("%d%s" % (int(v) >> 4, "MIDNSHP=X"[int(v) & 15]) for v in ops) if ncig[r] else "*")
     return AlignResult(as_[:n], xs[:n], seed[:n], strand[:n], pos[:n], nm[:n], cigars, st)
+
+
+class ProfileHits:
+    """The hits of sc_profile_hits in (segment, gene) order, one entry per hit in every array: seg, gene (indices), strand
+    (1: reverse), score (raw, may be x.5), identity, align_len, qfrom, qto, hfrom, hto (1-based), evalue."""
+    FIELDS = ("seg", "gene", "strand", "score", "identity", "align_len", "qfrom", "qto", "hfrom", "hto", "evalue")
+
+    def __init__(self, arrays, stats):
+        for k, v in zip(self.FIELDS, arrays):
+            setattr(self, k, v)
+        self.stats = stats
+
+    def __len__(self):
+        return len(self.seg)
+
+
+def _profile_call(gtext, gl, n_genes, segs, thresholds, device, cap):
+    import numpy as np
+    n = len(segs)
+    sl = np.array([0] + [len(x) for x in segs], dtype=np.int64).cumsum()
+    stext = b"".join(segs)
+    ip, lp, dp = C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_double)
+    while True:
+        ints = [np.zeros(max(cap, 1), dtype=np.int32) for _ in range(9)]
+        score, ev = np.zeros(max(cap, 1), dtype=np.float64), np.zeros(max(cap, 1), dtype=np.float64)
+        st, nh = ScProfileStats(), C.c_long()
+        iptr = [a.ctypes.data_as(ip) for a in ints]
+        rc = lib().sc_profile_hits(device, gtext, gl.ctypes.data_as(lp), n_genes, stext, sl.ctypes.data_as(lp), n, *thresholds, iptr[0],
+                                   iptr[1], iptr[2], score.ctypes.data_as(dp), iptr[3], iptr[4], iptr[5], iptr[6], iptr[7], iptr[8],
+                                   ev.ctypes.data_as(dp), cap, C.byref(nh), C.byref(st))
+        if rc == -5 and nh.value > cap:
+            cap = nh.value
+            continue
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_profile_error().decode())
+        k = nh.value
+        seg, gene, strand, identity, align_len, qfrom, qto, hfrom, hto = (a[:k] for a in ints)
+        return [seg, gene, strand, score[:k], identity, align_len, qfrom, qto, hfrom, hto, ev[:k]], st
+
+
+def profile_hits(genes, segs, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, device=0, cap=None):
+    """sc_profile_hits: every segment against every gene on both strands under blastn's 1/-2 scoring.
+    genes, segs: lists of bytes.  The room for hits starts at `cap` (default: 4 per segment, at least 65 536) and grows to
+    what the library asks for when it does not suffice.  Segments go to the library in stretches of at most 2^30 (segment,
+    gene, strand) tiles; the statistics are summed over the stretches."""
+    import numpy as np
+    gl = np.array([0] + [len(x) for x in genes], dtype=np.int64).cumsum()
+    gtext = b"".join(genes)
+    thresholds = (float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k))
+    step = max(1, (1 << 30) // (2 * max(len(genes), 1)))
+    parts, total = [], ScProfileStats()
+    for a in range(0, max(len(segs), 1), step):
+        chunk = segs[a:a + step]
+        arrays, st = _profile_call(gtext, gl, len(genes), chunk, thresholds, device, max(1 << 16, 4 * len(chunk)) if cap is None else int(cap))
+        arrays[0] = arrays[0] + a
+        parts.append(arrays)
+        for k, _ in ScProfileStats._fields_:
+            setattr(total, k, getattr(total, k) + getattr(st, k))
+    return ProfileHits([np.concatenate([p[f] for p in parts]) for f in range(11)], total)
