@@ -41,6 +41,23 @@ def device_hits(res):
              profile.format_evalue(float(res.evalue[k]))) for k in range(len(res))]
 
 
+def compare_hits(exe, genes, segs, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, name="hits", cap=None, exp=None):
+    """Every field of every hit, device against restatement (E as the hit CSV holds it), in (segment, gene) order; the first
+    five differing records with their segment lengths.  Returns (expected hits, capi.ProfileHits)."""
+    from rambl_amd import capi
+    if exp is None:
+        exp = run_hits_check(exe, genes, segs, min_identity, max_evalue, ka_lambda, ka_k)
+    exp = [as_csv_fields(h) for h in exp]
+    res = capi.profile_hits([g.encode() for g in genes], [s.encode() for s in segs], min_identity, max_evalue, ka_lambda, ka_k, cap=cap)
+    got = device_hits(res)
+    print("%s: thresholds -I %g -e %g: %d hits expected, %d from the device, %s" % (name, min_identity, max_evalue, len(exp), len(got), res.stats.as_dict()))
+    assert got == sorted(got, key=lambda h: h[:2])
+    bad = [(len(segs[e[0]]), e, g) for e, g in zip(exp, got) if e != g]
+    assert len(got) == len(exp) and not bad, "%s: %d expected, %d got, %d differ, first differences: %s" % (name, len(exp), len(got), len(bad), bad[:5])
+    assert res.stats.n_hits == len(exp)
+    return exp, res
+
+
 def rows_of(hits, seg_ids, seg_lens, gene_names):
     """The ten CSV columns (text) of restatement hits."""
     from rambl_amd import profile

@@ -44,3 +44,15 @@ def qual_string(rng, n, low=False):
     if low:
         return "".join(chr(33 + rng.randint(0, 40)) for _ in range(n))
     return "".join(chr(33 + rng.choice([30, 35, 38, 40, 41])) for _ in range(n))
+
+
+def device_rows(got):
+    """capi.AlignResult in the restatement's form."""
+    return [(int(got.as_[i]), int(got.xs[i]), int(got.seed[i]), int(got.strand[i]) if got.seed[i] >= 0 else 0, int(got.pos[i]),
+             got.cigar[i], int(got.nm[i])) for i in range(len(got.cigar))]
+
+
+def compare_rows(reads, exp, got_rows, name="reads"):
+    """Every field of every read, device against restatement; the first five differing records with their lengths."""
+    bad = [(i, len(reads[i][0]), e, g) for i, (e, g) in enumerate(zip(exp, got_rows)) if g != e]
+    assert len(got_rows) == len(exp) and not bad, "%s: %d of %d reads differ, first: %s" % (name, len(bad), len(exp), bad[:5])

@@ -20,15 +20,8 @@ def _gaps(h):
 
 
 def _compare(exe, genes, segs, min_identity, max_evalue):
-    from rambl_amd import capi
-    exp = [PL.as_csv_fields(h) for h in PL.run_hits_check(exe, genes, segs, min_identity, max_evalue)]
-    res = capi.profile_hits([g.encode() for g in genes], [s.encode() for s in segs], min_identity, max_evalue)
-    got = PL.device_hits(res)
-    print("thresholds -I %g -e %g: %d hits expected, %d from the device, %s" % (min_identity, max_evalue, len(exp), len(got), res.stats.as_dict()))
-    assert got == sorted(got, key=lambda h: h[:2])
-    bad = [(e, g) for e, g in zip(exp, got) if e != g]
-    assert len(got) == len(exp) and not bad, "%d expected, %d got, first differences: %s" % (len(exp), len(got), bad[:5])
-    assert res.stats.n_hits == len(exp) and res.stats.score_cells > 0 and res.stats.n_tiles > 0
+    exp, res = PL.compare_hits(exe, genes, segs, min_identity, max_evalue)
+    assert res.stats.score_cells > 0 and res.stats.n_tiles > 0
     return exp
 
 
