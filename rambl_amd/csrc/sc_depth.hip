@@ -20,7 +20,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +28,7 @@
 #include <vector>
 
 #include "../../include/straincall_hip.h"
+#include "sc_host.hpp"
 #include "sc_ingest.hpp"
 
 namespace {
@@ -199,18 +199,6 @@ __global__ __launch_bounds__(256) void k_depth_fused(const uint2* __restrict__ r
     }
 }
 
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    bool alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 16)) == hipSuccess; }
-};
-struct PinMem {
-    void* p = nullptr;
-    ~PinMem() { if (p) (void)hipHostFree(p); }
-    bool alloc(size_t n) { return hipHostMalloc(&p, std::max<size_t>(n, 16), hipHostMallocDefault) == hipSuccess; }
-};
-double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int host_threads() {
     long quota = 0;
     if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
@@ -226,83 +214,67 @@ int host_threads() {
 }
 
 // The device part: runs bucketed by reference (run_ptr[n_refs + 1]), 0-based inclusive (start, end) pairs; the runs of a
-// reference longer than a tile sorted by start.  `runs` is page-locked.
-int depth_scan_bucketed(int device, const int* ref_len, int n_refs, const unsigned* run_ptr, const uint2* runs, long n_runs, int max_run,
-                        int max_gap, int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap, int* n_intervals,
-                        sc_depth_stats* stats) {
-    DevMem d_runs, d_ptr, d_len, d_out, d_n, d_fix, d_cnt;
-    if (!d_runs.alloc(sizeof(uint2) * (size_t)n_runs) || !d_ptr.alloc(sizeof(unsigned) * ((size_t)n_refs + 1)) ||
-        !d_len.alloc(sizeof(int) * (size_t)n_refs) || !d_out.alloc(sizeof(Interval) * (size_t)std::max(cap, 1)) || !d_n.alloc(sizeof(int)) ||
-        !d_fix.alloc(sizeof(Interval) * (size_t)std::max(n_refs, 1) * FIXED) || !d_cnt.alloc(sizeof(int) * (size_t)std::max(n_refs, 1)))
-        return SC_ERR_HIP;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int rc = SC_OK;
-    auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = SC_ERR_HIP; };
-    chk(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (auto& e : ev) chk(hipEventCreate(&e));
-    if (rc == SC_OK) {
-        chk(hipEventRecord(ev[0], st));
-        if (n_runs > 0) chk(hipMemcpyAsync(d_runs.p, runs, sizeof(uint2) * (size_t)n_runs, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_ptr.p, run_ptr, sizeof(unsigned) * ((size_t)n_refs + 1), hipMemcpyHostToDevice, st));
-        if (n_refs > 0) chk(hipMemcpyAsync(d_len.p, ref_len, sizeof(int) * (size_t)n_refs, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(d_n.p, 0, sizeof(int), st));
-        chk(hipEventRecord(ev[1], st));
-        if (n_refs > 0) {
-            const int blocks = std::min((n_refs + 3) / 4, 1 << 16);         // four wavefronts per workgroup, one reference per wavefront
-            chk(hipEventRecord(ev[2], st));
-            if (max_gap >= 3)
-                hipLaunchKernelGGL(k_depth_fused<4>, dim3(blocks), dim3(256), 0, st, (const uint2*)d_runs.p, (const unsigned*)d_ptr.p,
-                                   (const int*)d_len.p, n_refs, max_gap, max_run, (Interval*)d_fix.p, (int*)d_cnt.p, (Interval*)d_out.p, cap, (int*)d_n.p);
-            else
-                hipLaunchKernelGGL(k_depth_fused<1>, dim3(blocks), dim3(256), 0, st, (const uint2*)d_runs.p, (const unsigned*)d_ptr.p,
-                                   (const int*)d_len.p, n_refs, max_gap, max_run, (Interval*)d_fix.p, (int*)d_cnt.p, (Interval*)d_out.p, cap, (int*)d_n.p);
-            chk(hipEventRecord(ev[3], st));
+// reference longer than a tile sorted by start.  `runs` is page-locked.  A failed HIP call throws sc::HipError.
+int depth_scan_bucketed(const int* ref_len, int n_refs, const unsigned* run_ptr, const uint2* runs, long n_runs, int max_run, int max_gap,
+                        int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap, int* n_intervals, sc_depth_stats* stats) {
+    sc::DevMem<uint2> d_runs((size_t)n_runs);
+    sc::DevMem<unsigned> d_ptr((size_t)n_refs + 1);
+    sc::DevMem<int> d_len((size_t)n_refs), d_n(1), d_cnt((size_t)n_refs);
+    sc::DevMem<Interval> d_out((size_t)std::max(cap, 0)), d_fix((size_t)n_refs * FIXED);
+    sc::TimedStream st;
+    st.mark("upload");
+    st.h2d(d_runs.p, runs, sizeof(uint2) * (size_t)n_runs);
+    st.h2d(d_ptr.p, run_ptr, sizeof(unsigned) * ((size_t)n_refs + 1));
+    st.h2d(d_len.p, ref_len, sizeof(int) * (size_t)n_refs);
+    st.zero(d_n.p, sizeof(int));
+    st.mark("uploaded");
+    if (n_refs > 0) {
+        const int blocks = std::min((n_refs + 3) / 4, 1 << 16);         // four wavefronts per workgroup, one reference per wavefront
+        st.mark("kernel");
+        if (max_gap >= 3)
+            hipLaunchKernelGGL(k_depth_fused<4>, dim3(blocks), dim3(256), 0, st, d_runs.p, d_ptr.p, d_len.p, n_refs, max_gap, max_run, d_fix.p,
+                               d_cnt.p, d_out.p, cap, d_n.p);
+        else
+            hipLaunchKernelGGL(k_depth_fused<1>, dim3(blocks), dim3(256), 0, st, d_runs.p, d_ptr.p, d_len.p, n_refs, max_gap, max_run, d_fix.p,
+                               d_cnt.p, d_out.p, cap, d_n.p);
+        st.mark("kernel done");
+    }
+    int n_more = 0;
+    std::vector<int> cnt((size_t)n_refs, 0);
+    std::vector<Interval> fix((size_t)n_refs * FIXED);
+    st.d2h(&n_more, d_n.p, sizeof(int));
+    st.d2h(cnt, d_cnt);
+    st.d2h(fix, d_fix);
+    st.sync();
+    st.launched();
+    long n = n_more;
+    for (int r = 0; r < n_refs; r++) n += cnt[(size_t)r];
+    *n_intervals = (int)std::min<long>(n, 0x7fffffffL);
+    if (n > cap) return SC_ERR_CAPACITY;
+    if (n > 0) {
+        if (!iv_ref || !iv_start || !iv_end || !iv_sum || !iv_n) return SC_ERR_ARG;
+        std::vector<Interval> iv;
+        iv.reserve((size_t)n);
+        for (int r = 0; r < n_refs; r++) for (int k = 0; k < cnt[(size_t)r]; k++) iv.push_back(fix[(size_t)r * FIXED + k]);
+        if (n_more > 0) {
+            const size_t at = iv.size();
+            iv.resize(at + (size_t)n_more);
+            HIPCHK(hipMemcpy(iv.data() + at, d_out.p, sizeof(Interval) * (size_t)n_more, hipMemcpyDeviceToHost));
         }
-        int n_more = 0;
-        std::vector<int> cnt((size_t)n_refs, 0);
-        std::vector<Interval> fix((size_t)n_refs * FIXED);
-        chk(hipMemcpyAsync(&n_more, d_n.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        if (n_refs > 0) {
-            chk(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(int) * (size_t)n_refs, hipMemcpyDeviceToHost, st));
-            chk(hipMemcpyAsync(fix.data(), d_fix.p, sizeof(Interval) * (size_t)n_refs * FIXED, hipMemcpyDeviceToHost, st));
-        }
-        chk(hipStreamSynchronize(st));
-        chk(hipGetLastError());
-        long n = n_more;
-        for (int r = 0; r < n_refs; r++) n += cnt[(size_t)r];
-        *n_intervals = (int)std::min<long>(n, 0x7fffffffL);
-        if (rc == SC_OK && n > cap) rc = SC_ERR_CAPACITY;
-        if (rc == SC_OK && n > 0) {
-            if (!iv_ref || !iv_start || !iv_end || !iv_sum || !iv_n) rc = SC_ERR_ARG;
-            else {
-                std::vector<Interval> iv;
-                iv.reserve((size_t)n);
-                for (int r = 0; r < n_refs; r++) for (int k = 0; k < cnt[(size_t)r]; k++) iv.push_back(fix[(size_t)r * FIXED + k]);
-                if (n_more > 0) {
-                    const size_t at = iv.size();
-                    iv.resize(at + (size_t)n_more);
-                    chk(hipMemcpy(iv.data() + at, d_out.p, sizeof(Interval) * (size_t)n_more, hipMemcpyDeviceToHost));
-                }
-                std::sort(iv.begin(), iv.end(), [](const Interval& a, const Interval& b) { return a.ref != b.ref ? a.ref < b.ref : a.start < b.start; });
-                for (long i = 0; i < n; i++) {
-                    iv_ref[i] = iv[(size_t)i].ref; iv_start[i] = iv[(size_t)i].start + 1; iv_end[i] = iv[(size_t)i].end + 1;      // 1-based, inclusive
-                    iv_sum[i] = (long)iv[(size_t)i].sum; iv_n[i] = iv[(size_t)i].n;
-                }
-            }
-        }
-        if (stats && rc == SC_OK) {
-            float ms = 0;
-            long cells = 0;
-            for (int r = 0; r < n_refs; r++) cells += ref_len[r];
-            stats->cells = cells; stats->runs = n_runs;
-            if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) stats->upload_ms = ms;
-            if (n_refs > 0 && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) stats->kernel_ms = ms;
+        std::sort(iv.begin(), iv.end(), [](const Interval& a, const Interval& b) { return a.ref != b.ref ? a.ref < b.ref : a.start < b.start; });
+        for (long i = 0; i < n; i++) {
+            iv_ref[i] = iv[(size_t)i].ref; iv_start[i] = iv[(size_t)i].start + 1; iv_end[i] = iv[(size_t)i].end + 1;      // 1-based, inclusive
+            iv_sum[i] = (long)iv[(size_t)i].sum; iv_n[i] = iv[(size_t)i].n;
         }
     }
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+    if (stats) {
+        long cells = 0;
+        for (int r = 0; r < n_refs; r++) cells += ref_len[r];
+        stats->cells = cells; stats->runs = n_runs;
+        stats->upload_ms = st.ms("upload", "uploaded");
+        if (n_refs > 0) stats->kernel_ms = st.ms("kernel", "kernel done");
+    }
+    return SC_OK;
 }
 
 // runs of a reference longer than a tile in start order (the kernel finds a tile's runs by binary search)
@@ -318,14 +290,14 @@ extern "C" {
 
 int sc_depth_scan_runs(int device, const int* ref_len, int n_refs, const int* run_ref, const int* run_start, const int* run_end,
                        long n_runs, int max_gap, int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap,
-                       int* n_intervals, sc_depth_stats* stats) {
+                       int* n_intervals, sc_depth_stats* stats) try {
     if (!ref_len || n_refs < 0 || n_runs < 0 || (n_runs > 0 && (!run_ref || !run_start || !run_end)) || max_gap < 0 || !n_intervals) return SC_ERR_ARG;
     if (n_runs > 0xFFFFFFF0L) return SC_ERR_CAPACITY;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SC_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return SC_ERR_HIP;
     if (stats) std::memset(stats, 0, sizeof *stats);
-    const double t0 = wall_ms();
+    const double t0 = sc::now_ms();
     for (int r = 0; r < n_refs; r++) if (ref_len[r] < 0) return SC_ERR_ARG;
     // bucket the runs by reference (a counting sort: the order inside a reference is kept)
     std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
@@ -335,9 +307,8 @@ int sc_depth_scan_runs(int device, const int* ref_len, int n_refs, const int* ru
         ptr[(size_t)r + 1]++;
     }
     for (int r = 0; r < n_refs; r++) ptr[(size_t)r + 1] += ptr[(size_t)r];
-    PinMem pin;
-    if (!pin.alloc(sizeof(uint2) * (size_t)n_runs)) return SC_ERR_HIP;
-    uint2* runs = (uint2*)pin.p;
+    sc::PinMem<uint2> pin((size_t)n_runs);
+    uint2* runs = pin.p;
     std::vector<unsigned> cur(ptr.begin(), ptr.end() - 1);
     int max_run = 1;
     for (long i = 0; i < n_runs; i++) {
@@ -345,13 +316,15 @@ int sc_depth_scan_runs(int device, const int* ref_len, int n_refs, const int* ru
         max_run = std::max(max_run, run_end[i] - run_start[i] + 1);
     }
     sort_long_refs(ref_len, n_refs, ptr.data(), runs);
-    if (stats) stats->prepare_ms = wall_ms() - t0;
-    return depth_scan_bucketed(device, ref_len, n_refs, ptr.data(), runs, n_runs, max_run, max_gap, iv_ref, iv_start, iv_end, iv_sum, iv_n,
-                               cap, n_intervals, stats);
+    if (stats) stats->prepare_ms = sc::now_ms() - t0;
+    return depth_scan_bucketed(ref_len, n_refs, ptr.data(), runs, n_runs, max_run, max_gap, iv_ref, iv_start, iv_end, iv_sum, iv_n, cap,
+                               n_intervals, stats);
+} catch (const sc::HipError&) {
+    return SC_ERR_HIP;
 }
 
 int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const* ref_names, const int* ref_len, int n_refs, int max_gap,
-                  int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap, int* n_intervals, sc_depth_stats* stats) {
+                  int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap, int* n_intervals, sc_depth_stats* stats) try {
     if (!alns || n_alns < 0 || !ref_names || !ref_len || n_refs < 0 || max_gap < 0 || !n_intervals) return SC_ERR_ARG;
     for (int f = 0; f < n_alns; f++) if (!alns[f]) return SC_ERR_ARG;
     int ndev = 0;
@@ -360,7 +333,7 @@ int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const
     if (stats) std::memset(stats, 0, sizeof *stats);
     // ---- the aligned runs of every reference, over all files: references are independent, so the host threads of this
     // rank take them in turns (the CIGAR walk of 10^7 records is the longest part of the stage once the device needs 0.1 ms)
-    const double t0 = wall_ms();
+    const double t0 = sc::now_ms();
     std::vector<std::vector<uint2>> per_ref((size_t)n_refs);
     std::atomic<int> next{0};
     std::atomic<int> max_run_all{1};
@@ -400,20 +373,21 @@ int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const
         work();
         for (auto& th : pool) th.join();
     }
-    if (stats) stats->extract_ms = wall_ms() - t0;
-    const double t1 = wall_ms();
+    if (stats) stats->extract_ms = sc::now_ms() - t0;
+    const double t1 = sc::now_ms();
     std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
     unsigned long long total = 0;
     for (int r = 0; r < n_refs; r++) { if (ref_len[r] < 0) return SC_ERR_ARG; total += per_ref[(size_t)r].size(); if (total > 0xFFFFFFF0ull) return SC_ERR_CAPACITY; ptr[(size_t)r + 1] = (unsigned)total; }
-    PinMem pin;
-    if (!pin.alloc(sizeof(uint2) * (size_t)total)) return SC_ERR_HIP;
-    uint2* runs = (uint2*)pin.p;
+    sc::PinMem<uint2> pin((size_t)total);
+    uint2* runs = pin.p;
     for (int r = 0; r < n_refs; r++)
         if (!per_ref[(size_t)r].empty()) std::memcpy(runs + ptr[(size_t)r], per_ref[(size_t)r].data(), sizeof(uint2) * per_ref[(size_t)r].size());
     sort_long_refs(ref_len, n_refs, ptr.data(), runs);
-    if (stats) stats->prepare_ms = wall_ms() - t1;
-    return depth_scan_bucketed(device, ref_len, n_refs, ptr.data(), runs, (long)total, max_run_all.load(), max_gap, iv_ref, iv_start, iv_end, iv_sum,
+    if (stats) stats->prepare_ms = sc::now_ms() - t1;
+    return depth_scan_bucketed(ref_len, n_refs, ptr.data(), runs, (long)total, max_run_all.load(), max_gap, iv_ref, iv_start, iv_end, iv_sum,
                                iv_n, cap, n_intervals, stats);
+} catch (const sc::HipError&) {
+    return SC_ERR_HIP;
 }
 
 }  // extern "C"

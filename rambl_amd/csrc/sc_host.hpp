@@ -16,7 +16,7 @@ struct ScError : std::runtime_error {
     int code;
     ScError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw HipError(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw ::sc::HipError(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -105,14 +105,52 @@ template <class T> struct HostMapped {                    // host memory the dev
     HostMapped(const HostMapped&) = delete;
     ~HostMapped() { (void)hipHostFree(p); }
 };
-template <class T> struct DevMem {
+template <class T> struct DevMem {                        // never null: an empty array is still a device address for a kernel
     T* p = nullptr;
-    explicit DevMem(size_t n) { HIPCHK(hipMalloc((void**)&p, n * sizeof(T))); }
+    explicit DevMem(size_t n) { HIPCHK(hipMalloc((void**)&p, std::max<size_t>(n * sizeof(T), 16))); }
     DevMem(const std::vector<T>& v) : DevMem(v.size()) {
         if (hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); throw HipError("hipMemcpy"); }
     }
     DevMem(const DevMem&) = delete;
     ~DevMem() { (void)hipFree(p); }
+};
+template <class T> struct PinMem {                        // page-locked host memory
+    T* p = nullptr;
+    explicit PinMem(size_t n) { HIPCHK(hipHostMalloc((void**)&p, std::max<size_t>(n * sizeof(T), 16), hipHostMallocDefault)); }
+    PinMem(const PinMem&) = delete;
+    ~PinMem() { (void)hipHostFree(p); }
+};
+// A stream of one call with the events that time its phases: mark(name) records one where the stream stands, ms(a, b) is
+// the device time between two of them once the stream was synchronised.  Copies of no bytes are left out.
+struct TimedStream {
+    Stream s;
+    std::vector<std::pair<const char*, hipEvent_t>> marks;
+    ~TimedStream() { for (auto& m : marks) (void)hipEventDestroy(m.second); }
+    operator hipStream_t() const { return s.st; }
+    void mark(const char* name) {
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreate(&e));
+        marks.emplace_back(name, e);
+        HIPCHK(hipEventRecord(e, s.st));
+    }
+    float ms(const char* a, const char* b) const {
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, event(a), event(b)));
+        return t;
+    }
+    void h2d(void* dst, const void* src, size_t n) { if (n) HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s.st)); }
+    void d2h(void* dst, const void* src, size_t n) { if (n) HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s.st)); }
+    template <class T> void h2d(DevMem<T>& d, const std::vector<T>& v) { h2d(d.p, v.data(), v.size() * sizeof(T)); }
+    template <class T> void d2h(std::vector<T>& v, const DevMem<T>& d) { d2h(v.data(), d.p, v.size() * sizeof(T)); }
+    void zero(void* dst, size_t n) { HIPCHK(hipMemsetAsync(dst, 0, n, s.st)); }
+    void launched() { HIPCHK(hipGetLastError()); }
+    void sync() { HIPCHK(hipStreamSynchronize(s.st)); }
+
+private:
+    hipEvent_t event(const char* name) const {
+        for (auto& m : marks) if (!strcmp(m.first, name)) return m.second;
+        throw HipError(std::string("no mark ") + name);
+    }
 };
 
 }  // namespace sc

@@ -1,5 +1,7 @@
 """Named edge cases of the two alignment kernel families: stage 4 (rambl_amd/csrc/sc_align.hip, restated in
 tests/native/sw_check.cpp) and the gene profile (rambl_amd/csrc/sc_profile.hip, restated in tests/native/blast_hits_check.cpp).
+Both run one sweep and one traceback window, rambl_amd/csrc/sc_wave_dp.hpp (sweep, trace_window, sweep_block); stage4_window
+and profile_window below restate that window, the launch limits are that header's.
 
 A case is a function of a seed.  It returns the inputs and a property check: a function of the restatement's output that
 raises unless the input reaches the edge the case is named for -- a generator that silently loses its edge fails on the CPU
@@ -16,7 +18,7 @@ import profile_lib as PL
 import stage4_lib as L
 
 MAX_READ, MAX_SEED, TB_COLS, GBAR = 512, 8192, 128, 4
-SCORE_BLOCKS, SCORE_WAVES, TRACE_BLOCKS = 16384, 4, 8192            # the launch limits of sc_align.hip / sc_profile.hip
+SCORE_BLOCKS, SCORE_WAVES, TRACE_BLOCKS = 16384, 4, 8192            # the launch limits of sc_wave_dp.hpp
 
 
 class Stage4Case:

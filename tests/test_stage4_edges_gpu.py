@@ -31,6 +31,13 @@ def test_case_equals_restatement(name, sw_check):
     L.compare_rows(case.reads, exp, L.device_rows(got), name)
     assert got.stats.n_traced == sum(e[2] >= 0 for e in exp)
     assert got.stats.score_cells == 2 * sum(len(r) for r, _ in case.reads) * sum(len(s) for s in case.seeds)
+    # block b of a window is swept from the window's first column, and stage 4 counts every block of every window
+    cells = 0
+    for (r, _), e in zip(case.reads, exp):
+        if e[2] >= 0:
+            w = E.stage4_window(len(r), e[0], e[4], e[5])
+            cells += (len(r) - E.clips(e[5])[1]) * sum(min(w["ncol"], E.TB_COLS * (b + 1)) for b in range(w["blocks"]))
+    assert got.stats.trace_cells == cells
 
 
 def test_read_order_does_not_matter():
