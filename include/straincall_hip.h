@@ -305,6 +305,38 @@ int sc_profile_hits(int device, const char* gene_text, const long* gene_off, int
                     double* evalue, long cap, long* n_hits, sc_profile_stats* stats);
 const char* sc_profile_error(void);
 
+/* The seeded mode of the gene profile: the same hits as sc_profile_hits, row for row, from the (segment, gene) pairs that
+ * share an exact k-mer only.  The reference never scores every pair either: its `blastn -word_size 22`
+ * (scripts/per_sample_gene_profile_fast.py:94-117) extends from exact word hits -- but a 22-mer loses hits, and the k here
+ * does not.  A hit that passes both thresholds has i identity columns and m others with i <= segment length,
+ * 100.0 * i / (i + m) >= min_identity_pct and 2 i - 4 m >= the least passing doubled score; the identity columns fall into
+ * at most m + 1 diagonal runs, so one run has ceil(i / (m + 1)) columns, a k-mer common to the gene and the segment on the
+ * hit's strand.  sc_profile_seed_length returns the least such bound over the given segment lengths that can pass at all
+ * (gene_bases: the sum of the gene lengths), at most 16 (2 bits per base in 32), and 0 where the bound is below 11 or no
+ * length can pass: the call then scores the full product as sc_profile_hits does (seed_k == 0).  *lossless_k (may be
+ * null): the bound before both clamps.  Lengths outside 1..512: SC_ERR_UNSUPPORTED (negative).
+ * A pair is the unit: when either strand shares a k-mer both strands of the pair are scored, since the better strand is
+ * chosen before the filters.  The genes' k-mers (forward strand, inside one gene, ACGT only) are indexed per call
+ * (DESIGN.md §8.10). */
+typedef struct sc_profile_seed_stats {
+    double upload_ms, score_ms, trace_ms, total_ms;      /* as in sc_profile_stats; score_ms of the pairs' tiles only */
+    long score_cells;      /* sum of 2 * segment length * gene length over the scored pairs (seed_k == 0: as sc_profile_stats) */
+    long trace_cells;
+    long n_tiles;          /* 2 * n_pairs (seed_k == 0: the full product) */
+    long n_candidates, n_traced, n_hits;
+    int seed_k;            /* the k-mer length of the call; 0: ran unseeded */
+    long n_gene_kmers;     /* k-mers of the genes in the index (one per window, repeats included) */
+    long n_pairs;          /* (segment, gene) pairs that share a k-mer on either strand */
+    double index_ms;       /* HIP events: the k-mer keys and their sort */
+    double lookup_ms;      /* HIP events: counting and filling the pair list, the host's scan between them included */
+} sc_profile_seed_stats;
+int sc_profile_hits_seeded(int device, const char* gene_text, const long* gene_off, int n_genes, const char* seg_text, const long* seg_off,
+                           int n_segs, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, int* hit_seg,
+                           int* hit_gene, int* hit_strand, double* hit_score, int* identity, int* align_len, int* qfrom, int* qto,
+                           int* hfrom, int* hto, double* evalue, long cap, long* n_hits, sc_profile_seed_stats* stats);
+int sc_profile_seed_length(const int* seg_len, int n_segs, long gene_bases, double min_identity_pct, double max_evalue, double ka_lambda,
+                           double ka_k, int* lossless_k);
+
 #ifdef __cplusplus
 }
 #endif

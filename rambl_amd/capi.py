@@ -47,6 +47,14 @@ class ScProfileStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScProfileSeedStats(C.Structure):
+    _fields_ = ScProfileStats._fields_ + [("seed_k", C.c_int), ("n_gene_kmers", C.c_long), ("n_pairs", C.c_long),
+                                          ("index_ms", C.c_double), ("lookup_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StrainCallError(RuntimeError):
     def __init__(self, code, msg=""):
         super().__init__("%s (%d)%s" % (ERRORS.get(code, "error"), code, (": " + msg) if msg else ""))
@@ -110,7 +118,10 @@ def load_library():
                                     dp, ip, ip, ip, ip, ip, ip, dp, C.c_long, lp, C.POINTER(ScProfileStats)]
     lib.sc_profile_error.argtypes = []
     lib.sc_profile_error.restype = cp
-    for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads", "sc_profile_hits"):
+    lib.sc_profile_hits_seeded.argtypes = lib.sc_profile_hits.argtypes[:-1] + [C.POINTER(ScProfileSeedStats)]
+    lib.sc_profile_seed_length.argtypes = [ip, C.c_int, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, ip]
+    for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads", "sc_profile_hits",
+              "sc_profile_hits_seeded", "sc_profile_seed_length"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
               "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level"):
@@ -122,7 +133,7 @@ EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "
            "sc_roi_graph_dump", "sc_roi_trace", "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align",
            "sc_roi_thread_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
            "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
-           "sc_align_error", "sc_profile_hits", "sc_profile_error"]
+           "sc_align_error", "sc_profile_hits", "sc_profile_error", "sc_profile_hits_seeded", "sc_profile_seed_length"]
 
 
 def default_params(error_rate=0.01, tau=0.02, diff_rate=0.01, graph_only=False, want_trace=False, want_timing=False, want_graph=False):
@@ -532,7 +543,7 @@ class ProfileHits:
         return len(self.seg)
 
 
-def _profile_call(gtext, gl, n_genes, segs, thresholds, device, cap):
+def _profile_call(gtext, gl, n_genes, segs, thresholds, device, cap, seeded=False):
     import numpy as np
     n = len(segs)
     sl = np.array([0] + [len(x) for x in segs], dtype=np.int64).cumsum()
@@ -541,9 +552,9 @@ def _profile_call(gtext, gl, n_genes, segs, thresholds, device, cap):
     while True:
         ints = [np.zeros(max(cap, 1), dtype=np.int32) for _ in range(9)]
         score, ev = np.zeros(max(cap, 1), dtype=np.float64), np.zeros(max(cap, 1), dtype=np.float64)
-        st, nh = ScProfileStats(), C.c_long()
+        st, nh = (ScProfileSeedStats if seeded else ScProfileStats)(), C.c_long()
         iptr = [a.ctypes.data_as(ip) for a in ints]
-        rc = lib().sc_profile_hits(device, gtext, gl.ctypes.data_as(lp), n_genes, stext, sl.ctypes.data_as(lp), n, *thresholds, iptr[0],
+        rc = (lib().sc_profile_hits_seeded if seeded else lib().sc_profile_hits)(device, gtext, gl.ctypes.data_as(lp), n_genes, stext, sl.ctypes.data_as(lp), n, *thresholds, iptr[0],
                                    iptr[1], iptr[2], score.ctypes.data_as(dp), iptr[3], iptr[4], iptr[5], iptr[6], iptr[7], iptr[8],
                                    ev.ctypes.data_as(dp), cap, C.byref(nh), C.byref(st))
         if rc == -5 and nh.value > cap:
@@ -556,22 +567,44 @@ def _profile_call(gtext, gl, n_genes, segs, thresholds, device, cap):
         return [seg, gene, strand, score[:k], identity, align_len, qfrom, qto, hfrom, hto, ev[:k]], st
 
 
-def profile_hits(genes, segs, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, device=0, cap=None):
+def profile_seed_length(seg_lens, gene_bases, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, lossless=False):
+    """sc_profile_seed_length (host only, no device): the k-mer length a seeded call over segments of these lengths and genes
+    of `gene_bases` bases in all uses, 0 when it runs unseeded.  lossless=True: the bound k* itself, before it is cut to 16 and
+    dropped below 11 (None when no length can pass)."""
+    import numpy as np
+    lens = np.ascontiguousarray(seg_lens, dtype=np.int32)
+    raw = C.c_int()
+    k = lib().sc_profile_seed_length(lens.ctypes.data_as(C.POINTER(C.c_int)), len(lens), int(gene_bases), float(min_identity), float(max_evalue),
+                                     float(ka_lambda), float(ka_k), C.byref(raw))
+    if k < 0:
+        raise StrainCallError(k)
+    return (raw.value or None) if lossless else k
+
+
+def profile_hits(genes, segs, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, device=0, cap=None, seeded=False):
     """sc_profile_hits: every segment against every gene on both strands under blastn's 1/-2 scoring.
     genes, segs: lists of bytes.  The room for hits starts at `cap` (default: 4 per segment, at least 65 536) and grows to
     what the library asks for when it does not suffice.  Segments go to the library in stretches of at most 2^30 (segment,
-    gene, strand) tiles; the statistics are summed over the stretches."""
+    gene, strand) tiles; the statistics are summed over the stretches.
+    seeded: sc_profile_hits_seeded, the same hits from the pairs that share a k-mer; the statistics are
+    ScProfileSeedStats, the genes are indexed again per stretch, and seed_k is the smallest of the stretches' (0 as soon as one
+    ran unseeded)."""
     import numpy as np
     gl = np.array([0] + [len(x) for x in genes], dtype=np.int64).cumsum()
     gtext = b"".join(genes)
     thresholds = (float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k))
     step = max(1, (1 << 30) // (2 * max(len(genes), 1)))
-    parts, total = [], ScProfileStats()
+    parts, total, seed_ks = [], (ScProfileSeedStats if seeded else ScProfileStats)(), []
     for a in range(0, max(len(segs), 1), step):
         chunk = segs[a:a + step]
-        arrays, st = _profile_call(gtext, gl, len(genes), chunk, thresholds, device, max(1 << 16, 4 * len(chunk)) if cap is None else int(cap))
+        arrays, st = _profile_call(gtext, gl, len(genes), chunk, thresholds, device, max(1 << 16, 4 * len(chunk)) if cap is None else int(cap),
+                                   seeded)
         arrays[0] = arrays[0] + a
         parts.append(arrays)
-        for k, _ in ScProfileStats._fields_:
+        for k, _ in total._fields_:
             setattr(total, k, getattr(total, k) + getattr(st, k))
+        if seeded:
+            seed_ks.append(st.seed_k)
+    if seeded:
+        total.seed_k = min(seed_ks)
     return ProfileHits([np.concatenate([p[f] for p in parts]) for f in range(11)], total)

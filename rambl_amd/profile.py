@@ -135,10 +135,11 @@ def format_table(sample, counts, relative=False):
 
 
 def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=MAX_EVALUE, relative=False, ka_lambda=KA_LAMBDA,
-                 ka_k=KA_K, out_dir=".", device=0, keep_hits=False, verbose=False):
+                 ka_k=KA_K, out_dir=".", device=0, keep_hits=False, verbose=False, seeded=False):
     """per_sample_gene_profile (:253-279) and the table of main (:324-336) for one sample.  Writes
     <out_dir>/<sample>_gene_count.tsv (and <sample>_hits.csv with `keep_hits`); returns the table path and the
-    sc_profile_stats of the device call(s)."""
+    sc_profile_stats of the device call(s).  seeded: only the (segment, gene) pairs that share a k-mer are scored
+    (sc_profile_hits_seeded): the same hits, the same files."""
     from . import samio
     fa = samio.Fasta(fasta)
     if not fa.order:
@@ -149,7 +150,7 @@ def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=
         segments = extract_segments(aln.walk())
     finally:
         aln.close()
-    hits = capi.profile_hits(genes, [s for _, s in segments], min_identity, max_evalue, ka_lambda, ka_k, device)
+    hits = capi.profile_hits(genes, [s for _, s in segments], min_identity, max_evalue, ka_lambda, ka_k, device, seeded=seeded)
     rows = hit_rows(hits, [q.decode() for q, _ in segments], [len(s) for _, s in segments], fa.order)
     counts = raw_abundance(rows, min_identity, max_evalue)
     os.makedirs(out_dir, exist_ok=True)
@@ -163,6 +164,10 @@ def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=
         import logging
         logging.info("profile of %s: %d segments against %d genes, %d hits, %d genes counted, %s", sample, len(segments), len(genes),
                      len(rows), len(counts), hits.stats.as_dict())
+        if seeded:
+            full = len(segments) * len(genes)
+            logging.info("seeded: seed_k %d%s, %d (segment, gene) pairs scored, %.4g %% of the full product of %d", hits.stats.seed_k,
+                         "" if hits.stats.seed_k else " (ran unseeded)", hits.stats.n_tiles // 2, 100.0 * (hits.stats.n_tiles // 2) / max(full, 1), full)
     return path, hits.stats
 
 
@@ -176,7 +181,9 @@ def main(argv=None):
     ap.add_argument("bam", metavar="SAMPLE_BAM", help="sample reads (SAM text or BAM)")
     ap.add_argument("sample", metavar="SAMPLE_NAME", help="sample name")
     ap.add_argument("-c", "--cores", dest="cores", type=int, default=1, help="CPU cores of the alignment-file reader [1]")
-    ap.add_argument("-w", "--word-size", dest="word_size", type=int, default=22, help="only 22: no word seeding happens")
+    ap.add_argument("-w", "--word-size", dest="word_size", type=int, default=22, help="only 22, and no word of that size is looked for: blastn's seeding loses hits. --seeded is the lossless counterpart")
+    ap.add_argument("--seeded", dest="seeded", action="store_true",
+                    help="score only the (segment, gene) pairs that share a k-mer, k chosen so that no hit is lost: the same output, less work")
     ap.add_argument("-R", "--reward", dest="reward", type=int, default=1, help="only 1")
     ap.add_argument("-P", "--penalty", dest="penalty", type=int, default=-2, help="only -2")
     ap.add_argument("-e", "--e-value", dest="e_value", type=float, default=MAX_EVALUE, help="e-value threshold [1e-10]")
@@ -203,7 +210,7 @@ def main(argv=None):
                  "without word seeding or a cap on alignments (got -w %d -R %d -P %d -A %d)" % (a.word_size, a.reward, a.penalty, a.max_num_align))
     os.environ["SC_INGEST_THREADS"] = str(max(1, min(a.cores, capi.host_plan(1)[2])))
     gene_profile(a.fasta, a.bam, a.sample, a.max_align_iden, a.e_value, a.relative_abundance, a.ka_lambda, a.ka_k, a.out_dir, a.device,
-                 a.keep_hits, a.verbose)
+                 a.keep_hits, a.verbose, a.seeded)
     return 0
 
 
