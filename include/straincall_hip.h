@@ -163,8 +163,8 @@ int sc_roi_thread_tables(sc_ctx* ctx, int handle, int* count, int* first_read, i
  * NonparametricClustering.cpp:230-249) through the production level kernel, on chosen inputs and
  * chosen uniforms.  S (2..128) strains with urn weights a0[S] and read log-likelihood rows
  * ll[s*n_reads + r], present where has[r] != 0; the level's n_ent entries (read ent_rid, copy number
- * ent_cn, one-symbol label ent_sym < 16) start at entry index e0 (the entries in front name other
- * reads); mates as a CSR over the reads (mate_off[n_reads+1], mate_idx, -1: none); n_sweeps sweeps,
+ * ent_cn, one-symbol label ent_sym < 16, or 0xFF: no single symbol, drawn but not counted) start
+ * at entry index e0 (the entries in front name other reads); mates as a CSR over the reads (mate_off[n_reads+1], mate_idx, -1: none); n_sweeps sweeps,
  * draw t taking U[t] (n_u >= n_sweeps * sum ent_cn <= 40000).  Out: kdraw[S] draws per strain,
  * cnt[S*16] draws per (strain, read symbol), out[5] = draws, draws of the fp64 scan tier, draws of
  * the literal tier, window passes, kernel variant.  Only on a context of one stream (SC_ERR_ARG

@@ -230,7 +230,9 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
     for (int s = 0; s < S; s++) if (!(a0[s] >= 0.0) || !std::isfinite(a0[s])) return SC_ERR_ARG;
     long Q = 0;
     for (int r = 0; r < n_ent; r++) {
-        if (ent_rid[r] < 0 || ent_rid[r] >= n_reads || ent_cn[r] < 1 || ent_sym[r] < 0 || ent_sym[r] >= KMAX) return SC_ERR_ARG;
+        // (a symbol code, or 0xFF: a label that is no single symbol, as JobDev::qcode marks it -- drawn, not counted)
+        const bool sym_ok = (ent_sym[r] >= 0 && ent_sym[r] < KMAX) || ent_sym[r] == 0xFF;
+        if (ent_rid[r] < 0 || ent_rid[r] >= n_reads || ent_cn[r] < 1 || !sym_ok) return SC_ERR_ARG;
         Q += ent_cn[r];
     }
     if (Q * n_sweeps > MAX_DRAWS || n_u < Q * n_sweeps) return SC_ERR_ARG;
@@ -261,7 +263,7 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         for (int r = 0, q = 0; r < n_ent; r++) { f.ent_cn[(size_t)(e0 + r)] = ent_cn[r]; qoff[(size_t)(e0 + r)] = q; q += ent_cn[r]; }
         const hipStream_t st = w.st;
         const std::vector<int> mptr(mate_off, mate_off + n_reads + 1), midx(mate_idx, mate_idx + nm);      // (alive until the copies are done)
-        JobDev jd = w.job_dev(w.passthrough, f, qoff, mptr, midx, n_reads, std::max<long>(Q, 1), n_ent);
+        JobDev jd = w.job_dev(w.passthrough, f, qoff, mptr, midx, n_reads, std::max<long>(Q, 1), n_ent, Q * n_sweeps);
         // rows as in the region set-up; strain s lives in row slot(s), not in row s
         auto slot = [](int s) { return (s * 37 + 5) % MAXS; };
         std::vector<double> rows((size_t)jd.ll_stride * MAXS, 0.0);

@@ -232,7 +232,7 @@ struct Worker {
     bool own_blocks = false;          // Ph / Pd / Rh are this worker's own allocations (a private worker: init_private)
     unsigned seq = 0;                 // stamp of the last level launched (the level server waits for it)
     DevBuf b_ent_rid, b_ent_cn, b_ent_lab_off, b_ent_lab_len, b_ent_first, b_ent_qoff, b_labels, b_mate_ptr, b_mate_idx,
-        b_ll, b_has, b_isnew, b_tabA, b_tabLf, b_qcode, b_qent, b_quid, b_out_ptr, b_out_node, b_pool_ptr, b_pool_rid,
+        b_ll, b_has, b_isnew, b_tabA, b_tabLf, b_qcode, b_qent, b_quid, b_dlog, b_out_ptr, b_out_node, b_pool_ptr, b_pool_rid,
         b_pool_cn, b_isend, b_esrc, b_support, b_jobdev;
     DevBuf m_seqs, m_off, m_cols0, m_cols1, m_counts, m_moves, m_trace, m_out, m_edge;
     PinnedArena* stage = nullptr;     // page-locked staging of the region's uploads / downloads: leased from the context
@@ -257,12 +257,15 @@ struct Worker {
     void thread_device(const std::string& G, const std::vector<AlignedRead>& R, const std::vector<std::vector<CigarOp>>& cig,
                        ThreadTables& T);
     JobDev job_dev(PinnedArena& ar, const FlatGraph& f, const std::vector<int>& ent_qoff, const std::vector<int>& mate_off,
-                   const std::vector<int>& mate_idx, int n_reads, long qcap, int max_entries);
+                   const std::vector<int>& mate_idx, int n_reads, long qcap, int max_entries, long max_draws);
     LevelItem level_item(const JobDev* job, const LevelHdr& H, int K) const {
         return LevelItem{job, H, level_kind(H) | (level_lds_kb(H, K) << 8), Pm, Rd};
     }
     void cluster(Job& job, const PoGraph& g, FlatGraph& f);
 };
+// Sweeps of a sampler level of Q draw slots (NonparametricClustering.cpp:160 / :781): what the walk runs and what the
+// region's draw log is sized for.
+inline int level_sweeps(const sc_params& pa, long Q) { return (int)std::min<long>(pa.sweeps_cap, pa.draw_budget / std::max<long>(Q, 1)); }
 // The mailbox a region walks its levels on (resident workers): handed on after its last level, or by an exception.
 struct MailHold {
     Worker* w;

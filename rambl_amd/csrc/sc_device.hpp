@@ -43,6 +43,8 @@ struct JobDev {
     int* qent;                   // [qcap] entry index of a draw slot
     int* quid;                   // [qcap] mate read id of a draw slot (-1 none)
     long qcap;
+    uint8_t* dlog;               // [dlog_cap] draw log of the sampler: the strain of draw t (rewritten every level)
+    long dlog_cap;               // the largest n_sweeps * Q of the region's levels
 };
 
 // Per-level parameters.  The scalars travel as kernel arguments (LevelHdr); the per-strain part lives

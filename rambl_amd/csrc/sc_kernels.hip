@@ -231,8 +231,11 @@ __device__ __noinline__ int slow_draw(const SlowArgs job, const int* s_slot, vol
 // window turn out to be.  The test adds eps*T on both sides for the fp32 error of
 // the chains and sums (< (2*S + 9) * 2^-24 relative to T).  Each pass accepts the
 // draws in front of the first one that fails the test (one LDS integer atomic per
-// accepted draw; the waves exchange the position through LDS) and the window
-// moves on to that draw, which then has p = 0 and margin eps*T only.  A draw that
+// accepted draw, on its strain's count, and one byte -- the strain -- stored to
+// the region's draw log in device memory, which no pass reads and no barrier
+// waits for: the draws per (strain, read symbol) are counted from the log after
+// the chain, draw_log_counts; the waves exchange the position through LDS) and
+// the window moves on to that draw, which then has p = 0 and margin eps*T only.  A draw that
 // fails at p = 0 is within the fp32 error bound of a boundary (or its row is NaN:
 // flagged slot): wave 0 sends it through the fp64 scan and, if needed, the literal
 // evaluation.
@@ -272,18 +275,23 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 constexpr int UWIN = 1024;     // uniforms staged in LDS (fp32), refilled in halves
 #ifdef SC_CHAIN_PROF
 // experiment builds only (make EXTRA=-DSC_CHAIN_PROF): where a pass of the chain spends its cycles, summed over every pass
-// of wave 0: [0] counts read + chains, [1] test + s_x write, [2] first barrier + advance, [3] commits, [4] second barrier,
-// [5] passes
+// of wave 0: [0] counts read + chains, [1] test + s_x write, [2] first barrier + advance, [3] commit section: bookkeeping
+// (ro, upos, uniform refill), [4] second barrier, [5] passes, and the rest of the commit section: [6] issue_loads, [7] the
+// s_kf commit, [8] the draw-log store.  The three stamps inside the commit section first wait for the LDS operations in
+// front of them (CHAIN_STAMP_W): what is asynchronous in the product build -- the next rows' LDS reads, the atomic -- is
+// charged to its own part here, so the parts add up to more than the section costs when they overlap.
 __device__ unsigned long long g_chain_prof[12];
 #define CHAIN_STAMP(k) do { if (wv == 0) { const unsigned long long t_ = clock64(); prof[k] += t_ - tprev; tprev = t_; } } while (0)
+#define CHAIN_STAMP_W(k) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); CHAIN_STAMP(k); } while (0)
 #else
 #define CHAIN_STAMP(k) do {} while (0)
+#define CHAIN_STAMP_W(k) do {} while (0)
 #endif
 
 template <int NQ, bool ROWS_LDS, int NW, class JD>
 __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, const StrainParam* s_sp, LevelResult* __restrict__ R,
                                             const int* s_slot, volatile double* s_a, volatile double* s_p, unsigned* s_kf,
-                                            const float* s_a0f, unsigned* s_cnt, int* s_x, float* s_uwin, const float* rows_lds, int stride, int tid) {
+                                            const float* s_a0f, int* s_x, float* s_uwin, const float* rows_lds, int stride, int tid) {
     constexpr int SPL = 4 * NQ, SP = 16 * NQ;               // strains per lane, capacity
     constexpr int NPLC = SP > 64 ? 2 : 1;                  // strains per lane in the checked tier
     constexpr float EPSW = (float)(SP + 16) * 1.5e-7f;     // (2*S + 9) * 2^-24 for the chains and sums + 3 * 2^-24 for the weights (exp_weight)
@@ -297,6 +305,7 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
     const SC_GLOBAL double* Ustream = (const SC_GLOBAL double*)job.U;
     const SC_GLOBAL float* Uf = (const SC_GLOBAL float*)job.Uf;
     const SC_GLOBAL float* rows_g = (const SC_GLOBAL float*)job.tabLf;
+    SC_GLOBAL unsigned char* dlog = (SC_GLOBAL unsigned char*)job.dlog;
     auto ld4 = [&](int idx) __attribute__((always_inline)) -> f4v {
         return ROWS_LDS ? *(const f4v*)(rows_lds + idx) : *(const SC_GLOBAL f4v*)(rows_g + idx);
     };
@@ -330,17 +339,15 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
     int upos = pos;                                        // (t + pos) & (UWIN - 1)
     f4v L[NQ];
     float uf = 0.0f, llast = 0.0f;
-    int sym = 0;                                           // read symbol of this lane's draw (kept behind the row)
     auto issue_loads = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int g = 0; g < NQ; g++) L[g] = ld4(ro + cbase + 4 * g);
         llast = ld1(ro + Sm1);
-        sym = __float_as_int(ld1(ro + S));
         uf = s_uwin[upos];
     };
     if (total > 0) issue_loads();
 #ifdef SC_CHAIN_PROF
-    unsigned long long prof[5] = {0, 0, 0, 0, 0}, tprev = clock64();
+    unsigned long long prof[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = clock64();
 #endif
 #pragma unroll 1
     while (t < total) {
@@ -436,12 +443,10 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
             adv = 1;
         }
         const bool acc = (pos < adv) && (k == 0);
-        const int cs = c * KMAX + sym;                       // draws per (strain, read symbol): the substitution counts of :198-206
-        const bool accs = acc && (sym < KMAX);
+        SC_GLOBAL unsigned char* const lg = dlog + (t + pos);     // acc: t + pos < total <= JobDev::dlog_cap
         t += adv;
         if (t >= total) {
-            if (acc) __hip_atomic_fetch_add(&s_kf[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (accs) __hip_atomic_fetch_add(&s_cnt[cs], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (acc) { __hip_atomic_fetch_add(&s_kf[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); *lg = (unsigned char)c; }
             break;
         }
         if (Q >= 16 * NW) {
@@ -466,17 +471,24 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
                 upf = false;
             }
         }
-        issue_loads();                                       // rows of the new window first, then the commit
-        if (acc) __hip_atomic_fetch_add(&s_kf[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (accs) __hip_atomic_fetch_add(&s_cnt[cs], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         CHAIN_STAMP(3);
+        issue_loads();                                       // rows of the new window first, then the commit
+        CHAIN_STAMP_W(6);
+        if (acc) __hip_atomic_fetch_add(&s_kf[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        CHAIN_STAMP_W(7);
+        // the draw's strain goes to the region's draw log: a vector-memory byte store, which the barrier below (LDS counter
+        // only) does not wait for.  The draws per (strain, read symbol) are counted from the log after the chain
+        // (draw_log_counts): no pass reads them.
+        if (acc) *lg = (unsigned char)c;
+        CHAIN_STAMP_W(8);
         lds_barrier();                                       // every wave's commits are in s_kf
         CHAIN_STAMP(4);
     }
 #ifdef SC_CHAIN_PROF
-    if (tid == 0) { for (int i = 0; i < 5; i++) atomicAdd(&g_chain_prof[i], prof[i]); atomicAdd(&g_chain_prof[5], n_pass); }
+    if (tid == 0) { for (int i = 0; i < 9; i++) if (i != 5) atomicAdd(&g_chain_prof[i], prof[i]); atomicAdd(&g_chain_prof[5], n_pass); }
 #endif
-    __syncthreads();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the draw log's stores have left this wavefront ...
+    __syncthreads();                                         // ... every wavefront's (draw_log_counts reads them)
     if (wv == 0) {
 #pragma unroll
         for (int i = 0; i < NPLC; i++) {
@@ -487,6 +499,49 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
             R->n_draws = (unsigned long long)total; R->n_exact = n_exact; R->n_slow = n_slow; R->n_pass = n_pass;
             R->chain_cycles = clock64() - clk0; R->chain_wall = wall_clock64() - wall0;
         }
+    }
+}
+
+// The draws per (strain, read symbol) -- the substitution counts of :198-206 -- out of the draw log, after the chain's
+// closing barrier, by every wavefront of the workgroup that is still there.  Draw t is the draw of slot t % Q, whose read
+// symbol is job.qcode[slot]; a symbol >= KMAX (no single symbol) is not counted.  A lane takes one slot and a stretch of
+// its sweeps (the whole column while there are more slots than lanes) and counts runs of one strain in a register: a read
+// prefers the same strain sweep after sweep, so a lane adds to s_cnt once per run, not once per draw, and the lanes of a
+// wavefront do so at different times -- no many-way conflicts on one address.  The log is rewritten every level, also by
+// a workgroup that stays on its CU (resident workers): the chain's wavefronts have drained their stores in front of the
+// barrier, and a device-scope acquire here keeps the L1 from serving a line of an earlier level.
+template <class JD>
+__device__ __forceinline__ void draw_log_counts(const JD& job, const LevelHdr& h, unsigned* s_cnt, int tid, int nt) {
+    const int Q = h.Q, n = h.n_sweeps;
+    if (Q <= 0 || n <= 0) return;                           // (no draws: uniform over the workgroup, like the chain's own loop)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const SC_GLOBAL unsigned char* dlog = (const SC_GLOBAL unsigned char*)job.dlog;
+    const int G = Q < nt ? min(nt / Q, n) : 1;              // stretches of sweeps per slot
+    const int per = (n + G - 1) / G;
+    for (int idx = tid; idx < Q * G; idx += nt) {
+        const int q = idx % Q, j0 = (idx / Q) * per, j1 = min(j0 + per, n);
+        const int sym = job.qcode[q];
+        if (sym >= KMAX || j0 >= j1) continue;
+        const SC_GLOBAL unsigned char* p = dlog + (j0 * Q + q);
+        int cur = 0;
+        unsigned run = 0;
+        auto count = [&](int c) __attribute__((always_inline)) {
+            if (c != cur) {
+                if (run) __hip_atomic_fetch_add(&s_cnt[cur * KMAX + sym], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                cur = c; run = 0;
+            }
+            run++;
+        };
+        int j = j0;
+        for (; j + 8 <= j1; j += 8, p += 8 * Q) {
+            int c[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) c[i] = p[i * Q] & (MAXS - 1);     // eight sweeps in flight (a strain index: s_cnt is [MAXS][KMAX])
+#pragma unroll
+            for (int i = 0; i < 8; i++) count(c[i]);
+        }
+        for (; j < j1; j++, p += Q) count(*p & (MAXS - 1));
+        if (run) __hip_atomic_fetch_add(&s_cnt[cur * KMAX + sym], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 }
 
@@ -864,7 +919,7 @@ __device__ __forceinline__ float exp_weight(double y) {
 }
 
 __host__ __device__ inline int chain_w_stride(int S) {
-    const int s4 = (S + 1 + 3) & ~3;                          // S weights + the read symbol
+    const int s4 = (S + 1 + 3) & ~3;                          // S weights + one zero (the row layout the kernel kinds' LDS limits were set with)
     return (s4 & 4) ? s4 : s4 + 4;                            // 4 * odd: conflict-free 16-byte row reads
 }
 
@@ -954,7 +1009,7 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
     if (tid == 0) R->phase_ticks[3] = (unsigned)(wall_clock64() - wall0);
 
     // what the sampler draws from.  Per draw slot q the fp32 weight row L[q][s] = exp(x_s - max_s x_s),
-    // x_s = ll(read) + ll(mate) in fp64, with the read's symbol behind it.  G lanes share a slot, each walks
+    // x_s = ll(read) + ll(mate) in fp64, zeros behind it up to the stride.  G lanes share a slot, each walks
     // <= 8 strains; the max is joined by shuffles.  A slot whose log-likelihoods lie in the underflow range of
     // the reference's exp() gets a NaN row, which sends its draws to the checked tiers.
     {
@@ -975,8 +1030,6 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
             const int rid = job.ent_rid[e0 + job.qent[q]], uid = job.quid[q];
             const bool hr = h.do_update ? true : job.has[rid] != 0;      // the update has just entered the level's reads
             const bool hu = uid >= 0 && job.has[uid] != 0;
-            const int c0 = job.qcode[q];
-            const float symf = __int_as_float(c0 < KMAX ? c0 : KMAX);    // the read symbol rides behind the weights (a tiny denormal under a zero count: no effect on the sums)
             const long Lf = (long)q * stride;
             auto cell = [&](int sx) __attribute__((always_inline)) -> double {
                 const double* row = job.ll + (long)l.s_slot[sx] * lstride;
@@ -1009,7 +1062,7 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
                             const int sx = s0 + i + k;
-                            const float wk = sx < S ? (flag ? qnanf : exp_weight(x[i + k] - m)) : (sx == S ? symf : 0.0f);
+                            const float wk = sx < S ? (flag ? qnanf : exp_weight(x[i + k] - m)) : 0.0f;
                             if (k == 0) w.x = wk; else if (k == 1) w.y = wk; else if (k == 2) w.z = wk; else w.w = wk;
                         }
                         put4(Lf + s0 + i, w);
@@ -1027,9 +1080,10 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
         if (!STAY) return;                                 // a finished wavefront no longer counts at the barriers below
         urn_chain_shadow<NW>(h, l.s_x);                    // ... one that has to stay takes part in them
     } else {
-        urn_chain_q<NB, ROWS_LDS, NW>(job, h, l.s_sp, R, l.s_slot, l.s_a, l.s_p, l.s_kf, l.s_a0f, l.s_cnt, l.s_x, s_uwin, s_rows, stride, tid);
+        urn_chain_q<NB, ROWS_LDS, NW>(job, h, l.s_sp, R, l.s_slot, l.s_a, l.s_p, l.s_kf, l.s_a0f, l.s_x, s_uwin, s_rows, stride, tid);
     }
     if (!STAY) nt = 64 * NW;
+    draw_log_counts(job, h, l.s_cnt, tid, nt);               // (behind the chain's closing barrier, by every wavefront still here)
     __syncthreads();
     for (int i = tid; i < S * KMAX; i += nt) R->cnt[i] = l.s_cnt[i];
     finish_level(h, R, wall0, tid);

@@ -146,9 +146,10 @@ void Worker::thread_device(const std::string& G, const std::vector<AlignedRead>&
 
 // The region's device block without what the caller sets itself (ll, has, U, Uf): the level-major entries of `f`, their
 // copy-number prefixes `ent_qoff` and the mates uploaded through `ar`, the level kernels' scratch sized for `qcap` draw
-// slots and `max_entries` entries at one level.
+// slots and `max_entries` entries at one level, the sampler's draw log for `max_draws` draws (the largest n_sweeps * Q of
+// the region's levels).
 JobDev Worker::job_dev(PinnedArena& ar, const FlatGraph& f, const std::vector<int>& ent_qoff, const std::vector<int>& mate_off,
-                       const std::vector<int>& mate_idx, int n_reads, long qcap, int max_entries) {
+                       const std::vector<int>& mate_idx, int n_reads, long qcap, int max_entries, long max_draws) {
     JobDev jd{};
     jd.ent_rid = upload(ar, b_ent_rid, f.ent_rid, st);
     jd.ent_cn = upload(ar, b_ent_cn, f.ent_cn, st);
@@ -168,6 +169,8 @@ JobDev Worker::job_dev(PinnedArena& ar, const FlatGraph& f, const std::vector<in
     jd.qcode = (uint8_t*)b_qcode.ensure((size_t)qcap + 8);
     jd.qent = (int*)b_qent.ensure(sizeof(int) * (size_t)qcap);
     jd.quid = (int*)b_quid.ensure(sizeof(int) * (size_t)qcap);
+    jd.dlog_cap = std::max<long>(max_draws, 1);
+    jd.dlog = (uint8_t*)b_dlog.ensure((size_t)jd.dlog_cap + 8);
     return jd;
 }
 
@@ -199,6 +202,11 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
     }
     { int qo = 0; for (int i = 0; i < n_reads; i++) { ent_qoff[final_e0 + i] = qo; qo += job.reads[i].cn; } }
     const long qcap = std::max<long>(std::max<long>(max_level_q, total_copies), 1);
+    // draws of the longest chain: n_sweeps * Q as np_bayes_clustering and read_assign form it (sc_walk.cpp), over the levels
+    // and the pseudo-level
+    auto level_draws = [&](long Q) { return (long)level_sweeps(job.params, Q) * Q; };
+    long max_draws = level_draws(total_copies);
+    for (int l = 0; l < f.n_levels; l++) max_draws = std::max(max_draws, level_draws(f.level_read_count[(size_t)l]));
     // cells of a read_loglik row that can hold a value when level l starts: the reads of the levels before it and their
     // mates (the soft update enters a mate the first time it is asked for, Strain.cpp:147-150) -- a prefix of the read ids
     std::vector<int> level_hi((size_t)f.n_levels + 1, 0);
@@ -213,7 +221,7 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
     }
 
     // ---- upload the static arrays; the rows start empty, the uniforms are the context's
-    JobDev jd = job_dev(*stage, f, ent_qoff, job.mate_off, job.mate_idx, n_reads, qcap, max_level_entries);
+    JobDev jd = job_dev(*stage, f, ent_qoff, job.mate_off, job.mate_idx, n_reads, qcap, max_level_entries, max_draws);
     jd.ll = (double*)b_ll.ensure(sizeof(double) * (size_t)jd.ll_stride * MAXS);
     jd.has = (uint8_t*)b_has.ensure((size_t)n_reads + 8);
     HIPCHK(hipMemsetAsync(jd.has, 0, (size_t)n_reads + 8, st));

@@ -304,6 +304,7 @@ struct LevelWalk {
             std::memcpy(dst, hm.lpc, sizeof(double) * (size_t)K * K);
         }
         const bool chain = (mode == MODE_SAMPLE) && S > 1 && n_sweeps > 0;
+        if (mode == MODE_SAMPLE && (long)n_sweeps * Q > jd.dlog_cap) throw ScError(SC_ERR_INTERNAL, "a level draws more than the region's draw log holds");
         const bool timed = chain && pa.want_timing && !w.grid;      // (no launch to bracket with events when the workers are resident)
         if (level_wants_grid(jd, H)) {
             // a very large level: row copies / the single-symbol update on a grid, from a device copy of the parameters
@@ -355,7 +356,7 @@ struct LevelWalk {
     // np_bayes_clustering, :128-244 (+ pruning :404-454)
     void np_bayes_clustering(int e0, int e1, int Q, bool has_dups, bool any_multi) {
         const int S = (int)level_strains.size();
-        const int n = std::min(pa.sweeps_cap, pa.draw_budget / Q);
+        const int n = level_sweeps(pa, Q);
         int last[MAXS];
         for (int s = 0; s < S; s++) {
             last[s] = s;
@@ -527,7 +528,7 @@ struct LevelWalk {
         const int S = (int)fs.size();
         if (S == 0) return;
         const int Q = (int)total_copies;
-        const int n = std::min(pa.sweeps_cap, pa.draw_budget / std::max(Q, 1));
+        const int n = level_sweeps(pa, Q);
         std::vector<ld> a(S);
         if (S == 1 || n <= 0) {
             for (int s = 0; s < S; s++) a[s] = fs[s].abundance;
