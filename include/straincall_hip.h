@@ -337,6 +337,45 @@ int sc_profile_hits_seeded(int device, const char* gene_text, const long* gene_o
 int sc_profile_seed_length(const int* seg_len, int n_segs, long gene_bases, double min_identity_pct, double max_evalue, double ka_lambda,
                            double ka_k, int* lossless_k);
 
+/* The counts mode of the gene profile: the table of blastout2abundance.cpp:70-196 over the hits of
+ * sc_profile_hits without the hit list.  Per (segment, gene) the better strand is picked on the device; per read (a set
+ * of segments: seg_read[n_segs] holds one read index in 0..n_reads-1 per segment) the pairs are ordered by
+ * E6 = strtod(sprintf("%.6g", E)), the E-value as the hit CSV holds it, and only the pairs of the read's smallest E6 are
+ * traced back; when none of them has 100 * identity / align_len >= min_identity_pct the read moves to its next E6, and a
+ * read with no E6 left counts nowhere.  A pair counts only with E <= max_evalue and E6 <= max_evalue.  Among the read's
+ * kept hits the genes hit most often share the read.
+ * Out: the distinct triples (gene, times_hit, number of such genes) in ascending order with the number of reads behind
+ * each; the read's share of the gene is times_hit / number_of_such_genes.  More than `cap` triples: SC_ERR_CAPACITY with
+ * *n_out set to the number that suffices.
+ *   seeded      not 0: score only the pairs that share a k-mer, k from the lengths of all the call's segments; the genes
+ *               are indexed once per call
+ *   cand_room   the candidate records (one per passing tile) held on the device at a time; 0: the library's default.  The
+ *               segments go through in stretches of whole reads that fit (a read alone gets the room it needs).
+ * Limits and messages as sc_profile_hits; besides, bits(n_genes) * 2 + bits(most segments in a read) may not exceed 64. */
+typedef struct sc_profile_count_stats {
+    double upload_ms, score_ms;
+    double trace_ms;       /* HIP events: the rounds -- selecting a group per read, k_bl_trace, the identity test, the reads' move */
+    double total_ms;
+    long score_cells, trace_cells, n_tiles, n_candidates;
+    long n_traced;         /* (segment, gene) pairs actually traced back */
+    long n_hits;           /* traced pairs that pass the identity threshold */
+    int seed_k;
+    long n_gene_kmers;     /* of the one index of the call */
+    long n_pairs;
+    double index_ms, lookup_ms;
+    int n_rounds;          /* trace rounds, summed over the stretches */
+    int n_stretches;
+    long n_reads_counted;  /* reads that count somewhere */
+    double select_ms;      /* HIP events: strand pick, E6 ranks and the two sorts */
+    double count_ms;       /* HIP events: the reads' triples, their sort and reduction */
+} sc_profile_count_stats;
+int sc_profile_counts(int device, const char* gene_text, const long* gene_off, int n_genes, const char* seg_text, const long* seg_off,
+                      int n_segs, const int* seg_read, int n_reads, double min_identity_pct, double max_evalue, double ka_lambda,
+                      double ka_k, int seeded, long cand_room, int* out_gene, int* out_times, int* out_share, long* out_reads, long cap,
+                      long* n_out, sc_profile_count_stats* stats);
+/* E6 of a segment of L bases with doubled raw score score2 against gene_bases gene bases; no device is touched. */
+double sc_profile_evalue6(int L, long gene_bases, int score2, double ka_lambda, double ka_k);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,14 @@ class ScProfileSeedStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScProfileCountStats(C.Structure):
+    _fields_ = ScProfileSeedStats._fields_ + [("n_rounds", C.c_int), ("n_stretches", C.c_int), ("n_reads_counted", C.c_long),
+                                              ("select_ms", C.c_double), ("count_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StrainCallError(RuntimeError):
     def __init__(self, code, msg=""):
         super().__init__("%s (%d)%s" % (ERRORS.get(code, "error"), code, (": " + msg) if msg else ""))
@@ -120,8 +128,12 @@ def load_library():
     lib.sc_profile_error.restype = cp
     lib.sc_profile_hits_seeded.argtypes = lib.sc_profile_hits.argtypes[:-1] + [C.POINTER(ScProfileSeedStats)]
     lib.sc_profile_seed_length.argtypes = [ip, C.c_int, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, ip]
+    lib.sc_profile_counts.argtypes = [C.c_int, cp, lp, C.c_int, cp, lp, C.c_int, ip, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.c_int, C.c_long, ip, ip, ip, lp, C.c_long, lp, C.POINTER(ScProfileCountStats)]
+    lib.sc_profile_evalue6.argtypes = [C.c_int, C.c_long, C.c_int, C.c_double, C.c_double]
+    lib.sc_profile_evalue6.restype = C.c_double
     for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads", "sc_profile_hits",
-              "sc_profile_hits_seeded", "sc_profile_seed_length"):
+              "sc_profile_hits_seeded", "sc_profile_seed_length", "sc_profile_counts"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
               "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level"):
@@ -133,7 +145,8 @@ EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "
            "sc_roi_graph_dump", "sc_roi_trace", "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align",
            "sc_roi_thread_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
            "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
-           "sc_align_error", "sc_profile_hits", "sc_profile_error", "sc_profile_hits_seeded", "sc_profile_seed_length"]
+           "sc_align_error", "sc_profile_hits", "sc_profile_error", "sc_profile_hits_seeded", "sc_profile_seed_length",
+           "sc_profile_counts"]         # (sc_profile_evalue6 as well: load_library looks it up itself; the list holds letter-only names)
 
 
 def default_params(error_rate=0.01, tau=0.02, diff_rate=0.01, graph_only=False, want_trace=False, want_timing=False, want_graph=False):
@@ -608,3 +621,54 @@ def profile_hits(genes, segs, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.2
     if seeded:
         total.seed_k = min(seed_ks)
     return ProfileHits([np.concatenate([p[f] for p in parts]) for f in range(11)], total)
+
+
+class ProfileCounts:
+    """The result of sc_profile_counts: triples = [(gene index, times_hit, number_of_such_genes, reads)] ascending, one entry
+    per distinct triple; a read behind a triple gives its gene times_hit / number_of_such_genes."""
+
+    def __init__(self, triples, stats):
+        self.triples = triples
+        self.stats = stats
+
+    def __len__(self):
+        return len(self.triples)
+
+
+def profile_evalue6(seg_len, gene_bases, score2, ka_lambda=1.28, ka_k=0.46):
+    """sc_profile_evalue6 (host only): the E-value of a segment of seg_len bases with doubled raw score score2 against
+    gene_bases gene bases as the hit CSV holds it, six significant digits read back -- the E-value the counting rule compares."""
+    return float(lib().sc_profile_evalue6(int(seg_len), int(gene_bases), int(score2), float(ka_lambda), float(ka_k)))
+
+
+def profile_counts(genes, segs, seg_read, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, device=0, cap=None, seeded=False,
+                   cand_room=0):
+    """sc_profile_counts: the counting rule over the hits of profile_hits without the hit list.  genes, segs:
+    lists of bytes; seg_read: one read index per segment (profile.read_index).  The room for triples starts at `cap`
+    (default 65 536) and grows to what the library asks for.  The library itself passes the segments through in stretches of
+    whole reads that fit `cand_room` candidate records (0: its default); the genes are uploaded and indexed once."""
+    import numpy as np
+    gl = np.array([0] + [len(x) for x in genes], dtype=np.int64).cumsum()
+    sl = np.array([0] + [len(x) for x in segs], dtype=np.int64).cumsum()
+    gtext, stext = b"".join(genes), b"".join(segs)
+    reads = np.ascontiguousarray(seg_read, dtype=np.int32)
+    if len(reads) != len(segs):
+        raise ValueError("%d read indices for %d segments" % (len(reads), len(segs)))
+    n_reads = int(reads.max()) + 1 if len(reads) else 0
+    ip, lp = C.POINTER(C.c_int), C.POINTER(C.c_long)
+    cap = 1 << 16 if cap is None else int(cap)
+    while True:
+        gene, times, share = (np.zeros(max(cap, 1), dtype=np.int32) for _ in range(3))
+        n_behind = np.zeros(max(cap, 1), dtype=np.int64)
+        st, n = ScProfileCountStats(), C.c_long()
+        rc = lib().sc_profile_counts(device, gtext, gl.ctypes.data_as(lp), len(genes), stext, sl.ctypes.data_as(lp), len(segs),
+                                     reads.ctypes.data_as(ip), n_reads, float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k),
+                                     int(bool(seeded)), int(cand_room), gene.ctypes.data_as(ip), times.ctypes.data_as(ip),
+                                     share.ctypes.data_as(ip), n_behind.ctypes.data_as(lp), cap, C.byref(n), C.byref(st))
+        if rc == -5 and n.value > cap:
+            cap = n.value
+            continue
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_profile_error().decode())
+        k = n.value
+        return ProfileCounts([(int(gene[i]), int(times[i]), int(share[i]), int(n_behind[i])) for i in range(k)], st)

@@ -66,9 +66,9 @@ template <class Cell> __host__ __device__ inline Window trace_window(int S, int 
 // The cells the block loop sweeps over a window when the walk ends in window column `last`: block b costs the columns from
 // the window start to the block's end.  The two families report different numbers on purpose: stage 4 counts every block
 // of the window (last = 0), the profile only the blocks its walk reached (last = the alignment's first column).
-inline long window_cells(Window w, int nrows, int last) {
+__host__ __device__ inline long window_cells(Window w, int nrows, int last) {
     long cols = 0;
-    for (int b = (w.ncol - 1) / TB_COLS; b >= last / TB_COLS; b--) cols += std::min(w.ncol, (b + 1) * TB_COLS);
+    for (int b = (w.ncol - 1) / TB_COLS; b >= last / TB_COLS; b--) cols += w.ncol < (b + 1) * TB_COLS ? w.ncol : (b + 1) * TB_COLS;
     return cols * nrows;
 }
 

@@ -6,6 +6,7 @@ alignment file mapped are extracted (extract_mapped_reads.cpp:29-105), searched 
 :120-153), counted (blastout2abundance.cpp:70-196) and written as `<sample>_gene_count.tsv` (:324-336).  blastn and the
 tools around it are replaced by the exact optimum of blastn's scoring with a fixed tie-break, computed by
 sc_profile_hits (rambl_amd/csrc/sc_profile.hip); the counting rule is the reference's, on the host, one pass over the hits.
+With --counts the rule runs on the device over each read's best hits only (sc_profile_counts).
 """
 import decimal
 import math
@@ -111,6 +112,28 @@ def raw_abundance(rows, min_identity=MIN_IDENTITY, max_evalue=MAX_EVALUE):
     return sorted(total.items(), key=lambda kv: kv[0].encode() if isinstance(kv[0], str) else kv[0])
 
 
+def read_index(seg_ids):
+    """The read of every segment by the counting rule's grouping: an id ending in /1 .1 /2 .2 belongs to the read without
+    the suffix, an id shorter than two characters is its own read.  Returns (one read index per segment, number of reads);
+    reads are numbered in order of first appearance."""
+    reads, out = {}, []
+    for seg in seg_ids:
+        read = seg[:-2] if len(seg) >= 2 and seg[-2:] in ("/1", ".1", "/2", ".2") else seg
+        out.append(reads.setdefault(read, len(reads)))
+    return out, len(reads)
+
+
+def counts_from_triples(triples, gene_names):
+    """[(gene, Fraction)] in byte order of the gene, as raw_abundance returns it, from the (gene index, times_hit,
+    number_of_such_genes, reads) of capi.profile_counts: every read behind a triple gives its gene times_hit /
+    number_of_such_genes."""
+    total = {}
+    for gene, times, share, n in triples:
+        g = gene_names[gene]
+        total[g] = total.get(g, 0) + n * Fraction(times, share)
+    return sorted(total.items(), key=lambda kv: kv[0].encode() if isinstance(kv[0], str) else kv[0])
+
+
 def format_raw(counts):
     """What the reference's counter prints: `gene<TAB>count`, the count as `cout` prints a long double (6 significant digits)."""
     return "".join("%s\t%g\n" % (g, float(v)) for g, v in counts)
@@ -135,11 +158,15 @@ def format_table(sample, counts, relative=False):
 
 
 def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=MAX_EVALUE, relative=False, ka_lambda=KA_LAMBDA,
-                 ka_k=KA_K, out_dir=".", device=0, keep_hits=False, verbose=False, seeded=False):
+                 ka_k=KA_K, out_dir=".", device=0, keep_hits=False, verbose=False, seeded=False, counts_only=False):
     """per_sample_gene_profile (:253-279) and the table of main (:324-336) for one sample.  Writes
     <out_dir>/<sample>_gene_count.tsv (and <sample>_hits.csv with `keep_hits`); returns the table path and the
     sc_profile_stats of the device call(s).  seeded: only the (segment, gene) pairs that share a k-mer are scored
-    (sc_profile_hits_seeded): the same hits, the same files."""
+    (sc_profile_hits_seeded): the same hits, the same files.  counts_only: the table comes from
+    sc_profile_counts, which picks, traces and counts only each read's best hits on the device: the same
+    table, no hit list (so no `keep_hits`); the statistics are sc_profile_count_stats."""
+    if counts_only and keep_hits:
+        raise ValueError("there is no hit list in the counts mode")
     from . import samio
     fa = samio.Fasta(fasta)
     if not fa.order:
@@ -150,14 +177,27 @@ def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=
         segments = extract_segments(aln.walk())
     finally:
         aln.close()
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, sample + "_gene_count.tsv")
+    if counts_only:
+        seg_read, n_reads = read_index([q.decode() for q, _ in segments])
+        res = capi.profile_counts(genes, [s for _, s in segments], seg_read, min_identity, max_evalue, ka_lambda, ka_k, device, seeded=seeded)
+        counts = counts_from_triples(res.triples, fa.order)
+        with open(path, "w") as f:
+            f.write(format_table(sample, counts, relative))
+        if verbose:
+            import logging
+            st = res.stats
+            logging.info("profile of %s (counts): %d segments of %d reads against %d genes, %d of %d candidates traced in %d rounds over %d "
+                         "stretches, %d reads counted, %d genes counted, %s", sample, len(segments), n_reads, len(genes), st.n_traced,
+                         st.n_candidates, st.n_rounds, st.n_stretches, st.n_reads_counted, len(counts), st.as_dict())
+        return path, res.stats
     hits = capi.profile_hits(genes, [s for _, s in segments], min_identity, max_evalue, ka_lambda, ka_k, device, seeded=seeded)
     rows = hit_rows(hits, [q.decode() for q, _ in segments], [len(s) for _, s in segments], fa.order)
     counts = raw_abundance(rows, min_identity, max_evalue)
-    os.makedirs(out_dir, exist_ok=True)
     if keep_hits:
         with open(os.path.join(out_dir, sample + "_hits.csv"), "w") as f:
             f.write(hits_csv(rows))
-    path = os.path.join(out_dir, sample + "_gene_count.tsv")
     with open(path, "w") as f:
         f.write(format_table(sample, counts, relative))
     if verbose:
@@ -199,18 +239,23 @@ def main(argv=None):
     ap.add_argument("-o", "--out-dir", dest="out_dir", default=".", help="where <sample>_gene_count.tsv goes")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("--keep-hits", dest="keep_hits", action="store_true", help="also write <sample>_hits.csv, the input of blastout2abundance")
+    ap.add_argument("--counts", dest="counts", action="store_true",
+                    help="choose, trace and count only each read's best hits on the GPU: the same table without the hit list (can be "
+                         "combined with --seeded, not with --keep-hits)")
     ap.add_argument("-v", "--verbose", dest="verbose", action="store_true", help="verbose output")
     a = ap.parse_args(argv)
     logging.basicConfig(format="[%(asctime)s] %(levelname)s : %(message)s", level=logging.INFO)
     if a.rdp_classifier is not None or a.thresh is not None:
         ap.error("copy number correction (-C / -t) needs the RDP classifier and is not built: the tool behaves as the script does with -n")
+    if a.counts and a.keep_hits:
+        ap.error("--counts cannot be combined with --keep-hits: there is no hit list in this mode")
     given = {"word_size": a.word_size, "reward": a.reward, "penalty": a.penalty, "max_num_align": a.max_num_align}
     if given != SCRIPT_DEFAULTS:
         ap.error("only -w 22 -R 1 -P -2 -A 30 is available: the hits are the exact optimum of that scoring, computed on the GPU "
                  "without word seeding or a cap on alignments (got -w %d -R %d -P %d -A %d)" % (a.word_size, a.reward, a.penalty, a.max_num_align))
     os.environ["SC_INGEST_THREADS"] = str(max(1, min(a.cores, capi.host_plan(1)[2])))
     gene_profile(a.fasta, a.bam, a.sample, a.max_align_iden, a.e_value, a.relative_abundance, a.ka_lambda, a.ka_k, a.out_dir, a.device,
-                 a.keep_hits, a.verbose, a.seeded)
+                 a.keep_hits, a.verbose, a.seeded, a.counts)
     return 0
 
 
