@@ -270,7 +270,7 @@ int sc_align_reads(int device, const char* seed_text, const long* seed_off, int 
                    int cigar_stride, int* n_cigar, sc_align_stats* stats);
 const char* sc_align_error(void);
 
-/* ---- the per-sample gene profile on the device (rambl_amd/csrc/sc_profile.hip) ---------------------------------
+/* ---- the per-sample gene profile on the device (rambl_amd/csrc/sc_profile.hip and sc_profile_*.hpp) -------------
  *
  * scripts/per_sample_gene_profile_fast.py:80-153 searches a sample's read segments in the assembled genes with
  * makeblastdb and `blastn -reward 1 -penalty -2` and turns the XML into a CSV with bigBlastParser and sqlite3.

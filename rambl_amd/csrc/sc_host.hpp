@@ -42,6 +42,12 @@ struct DevBuf {
     }
     ~DevBuf() { if (p) (void)hipFree(p); for (void* q : outgrown) (void)hipFree(q); }
 };
+// A DevBuf of T: ensure(n) is room for n elements (null while nothing was ever asked for), get() the array as it stands.
+template <class T> struct DevArr {
+    DevBuf b;
+    T* ensure(size_t n) { return (T*)b.ensure(n * sizeof(T)); }
+    T* get() const { return (T*)b.p; }
+};
 // Pinned staging for a region's transfers.  A copy between the device and ordinary (pageable) host memory makes the
 // runtime pin those pages for the copy and let them go afterwards; with regions in flight that costs far more than the
 // copy -- registering and releasing user pages suspends every queue of the process (level kernels of ALL regions lasting

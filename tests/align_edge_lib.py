@@ -1,5 +1,5 @@
 """Named edge cases of the two alignment kernel families: stage 4 (rambl_amd/csrc/sc_align.hip, restated in
-tests/native/sw_check.cpp) and the gene profile (rambl_amd/csrc/sc_profile.hip, restated in tests/native/blast_hits_check.cpp).
+tests/native/sw_check.cpp) and the gene profile (rambl_amd/csrc/sc_profile.hip and sc_profile_dp.hpp, restated in tests/native/blast_hits_check.cpp).
 Both run one sweep and one traceback window, rambl_amd/csrc/sc_wave_dp.hpp (sweep, trace_window, sweep_block); stage4_window
 and profile_window below restate that window, the launch limits are that header's.
 

@@ -13,8 +13,8 @@ import profile_lib as PL
 import stage4_lib as L
 from align_edge_lib import need
 
-COUNT_ROUNDS = 3                        # sc_profile.hip: rounds of one group per read before the rest is traced at once
-REC_BLOCKS, READ_BLOCKS = 256, 8192     # sc_profile.hip: blocks of 256 threads, a record each / of one wavefront, a read each
+COUNT_ROUNDS = 3                        # sc_profile_counts.hpp: rounds of one group per read before the rest is traced at once
+REC_BLOCKS, READ_BLOCKS = 256, 8192     # sc_profile_counts.hpp: blocks of 256 threads, a record each / of one wavefront, a read each
 DEFAULTS = (95.0, 1e-10, 1.28, 0.46)
 SUFFIXES = ("/1", ".1", "/2", ".2")
 

@@ -1,5 +1,5 @@
 """GPU: the counts mode of the gene profile (sc_profile_counts: k_cnt_* around k_bl_score / k_bl_trace in
-rambl_amd/csrc/sc_profile.hip) against the counting rule on the plain restatement's hits
+rambl_amd/csrc/sc_profile_counts.hpp) against the counting rule on the plain restatement's hits
 (tests/count_lib.py): exact Fractions and equal triples, unseeded and seeded, on the data sets and on every named edge."""
 import os
 import random
@@ -59,6 +59,24 @@ def test_stretches(seeded, hits_check):
     # one read per stretch when the room holds no more
     tiny = CL.device_counts(case, seeded, cand_room=1)
     assert tiny.triples == whole.triples and tiny.stats.n_stretches > 100
+
+
+@MODES
+def test_one_score_pass_behind_every_entry_point(seeded):
+    """The hit list's and the counts' entry points score the same tiles: equal statistics of the score pass on the same input,
+    in one stretch and summed over three or more."""
+    from rambl_amd import capi
+    case = CL.case("parity")
+    hits = capi.profile_hits([g.encode() for g in case.genes], [s.encode() for s in case.segs], *case.thresholds, seeded=seeded).stats
+    fields = ("n_tiles", "n_candidates", "score_cells") + (("seed_k", "n_pairs", "n_gene_kmers") if seeded else ())
+    expected = [getattr(hits, f) for f in fields]
+    print("hits%s: %s" % (" seeded" if seeded else "", dict(zip(fields, expected))))
+    assert hits.n_tiles > 0 and hits.n_candidates > 0 and (not seeded or hits.seed_k == 13)
+    whole = CL.device_counts(case, seeded).stats
+    parts = CL.device_counts(case, seeded, cand_room=2 * len(case.genes) * len(case.segs) // 4).stats
+    assert whole.n_stretches == 1 and parts.n_stretches >= 3
+    assert [getattr(whole, f) for f in fields] == expected
+    assert [getattr(parts, f) for f in fields] == expected
 
 
 def test_capacity_reaches_the_binding_and_grows(hits_check):

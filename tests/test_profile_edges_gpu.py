@@ -1,5 +1,5 @@
 """GPU: the named edge cases of tests/align_edge_lib.py through k_bl_score<1..8> / k_bl_trace<1..8>
-(rambl_amd/csrc/sc_profile.hip) against the plain restatement (tests/native/blast_hits_check.cpp): every field of every hit,
+(rambl_amd/csrc/sc_profile.hip, sc_profile_dp.hpp) against the plain restatement (tests/native/blast_hits_check.cpp): every field of every hit,
 exactly, E through profile.format_evalue.  `every_bucket` launches every instantiation, `score_stride` and `trace_stride`
 the second trip of the two grid-stride loops."""
 import math

@@ -1,4 +1,4 @@
-"""GPU: the hits of the per-sample gene profile on the device (rambl_amd/csrc/sc_profile.hip) against the plain restatement
+"""GPU: the hits of the per-sample gene profile on the device (rambl_amd/csrc/sc_profile.hip, sc_profile_dp.hpp) against the plain restatement
 of the contract (tests/native/blast_hits_check.cpp), its limits, and the profile of three mixed samples end to end."""
 import os
 

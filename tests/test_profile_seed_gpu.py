@@ -1,5 +1,5 @@
 """GPU: the seeded gene profile (sc_profile_hits_seeded: k_seed_keys, k_seed_lookup, k_bl_score_pairs in
-rambl_amd/csrc/sc_profile.hip) against the unseeded call and the plain restatements: equal hits field by
+rambl_amd/csrc/sc_profile_seed.hpp and sc_profile_dp.hpp) against the unseeded call and the plain restatements: equal hits field by
 field, and the pair list's size, cells and tiles against tests/seed_lib.py wherever the call was seeded."""
 import math
 import os
@@ -15,7 +15,7 @@ import stage4_lib as L
 pytestmark = pytest.mark.gpu
 
 DEFAULTS = (95.0, 1e-10, 1.28, 0.46)
-LOOKUP_BLOCKS = 8192                                                  # sc_profile.hip: blocks of one wavefront, one segment each
+LOOKUP_BLOCKS = 8192                                                  # sc_profile_seed.hpp: blocks of one wavefront, one segment each
 
 
 @pytest.fixture(scope="module")
@@ -75,6 +75,21 @@ def test_identity_90_runs_unseeded(parity):
     genes, segs, _ = parity
     hits, res, pairs = both_modes(genes[:6], segs[:150], (90.0, 1e-10, 1.28, 0.46), name="I 90")
     assert pairs is None and res.stats.seed_k == 0 and res.stats.n_tiles == 2 * 150 * 6 and len(hits) > 20
+
+
+def test_unseeded_run_reports_what_the_plain_entry_point_does(parity):
+    """seed_k == 0: sc_profile_hits_seeded's counters are sc_profile_hits's on the same call, and what is the seeded mode's
+    own stays 0."""
+    from rambl_amd import capi
+    genes, segs, _ = parity
+    genes, segs, thresholds = genes[:6], segs[:150], (90.0, 1e-10, 1.28, 0.46)
+    assert capi.profile_seed_length([len(s) for s in segs], sum(len(g) for g in genes), *thresholds) == 0     # no device needed
+    plain, seeded = _run(genes, segs, thresholds, False).stats, _run(genes, segs, thresholds, True).stats
+    print("plain %s\nseeded %s" % (plain.as_dict(), seeded.as_dict()))
+    assert seeded.seed_k == 0 and plain.n_tiles == 2 * 150 * 6 and plain.n_hits > 20 and plain.trace_cells > 0
+    for field in ("score_cells", "trace_cells", "n_tiles", "n_candidates", "n_traced", "n_hits"):
+        assert getattr(seeded, field) == getattr(plain, field), field
+    assert seeded.n_pairs == 0 and seeded.n_gene_kmers == 0 and seeded.index_ms == 0 and seeded.lookup_ms == 0
 
 
 @pytest.mark.parametrize("name", sorted(E.PROFILE_CASES))
