@@ -224,7 +224,10 @@ void sc_reads_free(sc_reads* reads);
  * kernel: the per-base depth never exists in HBM, a wavefront builds it for its reference in LDS):
  * intervals come back sorted by (reference index, start), 1-based inclusive, with the sum of the depths of their
  * covered positions and their number (mean = sum / n).  Returns SC_ERR_CAPACITY (with *n_intervals set) when `cap`
- * is too small.  samtools' per-file depth cap (8000) is not applied; parity at that tool boundary is unpinned. */
+ * is too small.  samtools' per-file depth cap (8000) is not applied; parity at that tool boundary is unpinned.
+ * Limits, checked before anything is launched (SC_ERR_ARG): 0 <= max_gap <= SC_DEPTH_MAX_GAP and no reference longer than
+ * 2^30 bases -- the kernel keeps positions and "no position yet" (-2^30) in int and compares with max_gap + 1. */
+#define SC_DEPTH_MAX_GAP ((1 << 30) - (1 << 24))
 typedef struct sc_depth_stats {
     long cells;            /* reference bases scanned */
     long runs;             /* aligned runs (CIGAR M = X operations) */

@@ -70,6 +70,15 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
 
 constexpr int TILE = 2048;          // cells of a wavefront's LDS tile
 
+// What the entry points accept of max_gap and of a reference's length.  k_depth_fused marks "no covered position yet" with
+// NONE = -2^30 and starts an interval at position p behind the last covered position `prev` iff p - prev > max_gap + 1, both
+// sides in int.  With prev = NONE the left side is p + 2^30: it must not overflow (p <= 2^30 - 1, so len <= 2^30) and must
+// exceed max_gap + 1 for every p >= 0 (max_gap <= 2^30 - 2), or a reference's first covered position starts no interval.
+// With prev >= 0 both sides stay inside 0..2^30.  NONE itself only passes through max() with positions and NONE.  The limit on
+// max_gap keeps 2^24 of room below that bound.
+constexpr int MAX_GAP_LIMIT = SC_DEPTH_MAX_GAP, MAX_REF_LEN = 1 << 30;
+static_assert(MAX_GAP_LIMIT <= (1 << 30) - 2, "NONE = -2^30 has to lie more than max_gap + 1 in front of position 0");
+
 // PPL positions per lane and step: 4 (one 16-byte LDS read) while no interval can break inside four consecutive
 // positions (max_gap >= 3), else 1.
 template <int PPL>
@@ -82,7 +91,7 @@ __global__ __launch_bounds__(256) void k_depth_fused(const uint2* __restrict__ r
     int* tile = s_tile[threadIdx.x >> 6];
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    constexpr int NONE = -(1 << 30);
+    constexpr int NONE = -(1 << 30);       // (MAX_GAP_LIMIT and MAX_REF_LEN are derived from this value)
     for (int ref = wave; ref < n_refs; ref += nwaves) {
         const int len = ref_len[ref];
         const unsigned rp0 = run_ptr[ref], rp1 = run_ptr[ref + 1];
@@ -277,6 +286,12 @@ int depth_scan_bucketed(const int* ref_len, int n_refs, const unsigned* run_ptr,
     return SC_OK;
 }
 
+bool depth_limits_ok(const int* ref_len, int n_refs, int max_gap) {
+    if (max_gap < 0 || max_gap > MAX_GAP_LIMIT) return false;
+    for (int r = 0; r < n_refs; r++) if (ref_len[r] < 0 || ref_len[r] > MAX_REF_LEN) return false;
+    return true;
+}
+
 // runs of a reference longer than a tile in start order (the kernel finds a tile's runs by binary search)
 void sort_long_refs(const int* ref_len, int n_refs, const unsigned* run_ptr, uint2* runs) {
     for (int r = 0; r < n_refs; r++)
@@ -291,14 +306,14 @@ extern "C" {
 int sc_depth_scan_runs(int device, const int* ref_len, int n_refs, const int* run_ref, const int* run_start, const int* run_end,
                        long n_runs, int max_gap, int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap,
                        int* n_intervals, sc_depth_stats* stats) try {
-    if (!ref_len || n_refs < 0 || n_runs < 0 || (n_runs > 0 && (!run_ref || !run_start || !run_end)) || max_gap < 0 || !n_intervals) return SC_ERR_ARG;
+    if (!ref_len || n_refs < 0 || n_runs < 0 || (n_runs > 0 && (!run_ref || !run_start || !run_end)) || !n_intervals) return SC_ERR_ARG;
+    if (!depth_limits_ok(ref_len, n_refs, max_gap)) return SC_ERR_ARG;
     if (n_runs > 0xFFFFFFF0L) return SC_ERR_CAPACITY;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SC_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return SC_ERR_HIP;
     if (stats) std::memset(stats, 0, sizeof *stats);
     const double t0 = sc::now_ms();
-    for (int r = 0; r < n_refs; r++) if (ref_len[r] < 0) return SC_ERR_ARG;
     // bucket the runs by reference (a counting sort: the order inside a reference is kept)
     std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
     for (long i = 0; i < n_runs; i++) {
@@ -325,7 +340,8 @@ int sc_depth_scan_runs(int device, const int* ref_len, int n_refs, const int* ru
 
 int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const* ref_names, const int* ref_len, int n_refs, int max_gap,
                   int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap, int* n_intervals, sc_depth_stats* stats) try {
-    if (!alns || n_alns < 0 || !ref_names || !ref_len || n_refs < 0 || max_gap < 0 || !n_intervals) return SC_ERR_ARG;
+    if (!alns || n_alns < 0 || !ref_names || !ref_len || n_refs < 0 || !n_intervals) return SC_ERR_ARG;
+    if (!depth_limits_ok(ref_len, n_refs, max_gap)) return SC_ERR_ARG;
     for (int f = 0; f < n_alns; f++) if (!alns[f]) return SC_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SC_ERR_NO_DEVICE;
@@ -377,7 +393,7 @@ int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const
     const double t1 = sc::now_ms();
     std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
     unsigned long long total = 0;
-    for (int r = 0; r < n_refs; r++) { if (ref_len[r] < 0) return SC_ERR_ARG; total += per_ref[(size_t)r].size(); if (total > 0xFFFFFFF0ull) return SC_ERR_CAPACITY; ptr[(size_t)r + 1] = (unsigned)total; }
+    for (int r = 0; r < n_refs; r++) { total += per_ref[(size_t)r].size(); if (total > 0xFFFFFFF0ull) return SC_ERR_CAPACITY; ptr[(size_t)r + 1] = (unsigned)total; }
     sc::PinMem<uint2> pin((size_t)total);
     uint2* runs = pin.p;
     for (int r = 0; r < n_refs; r++)

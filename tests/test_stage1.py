@@ -1,5 +1,6 @@
 """rambl.py stage 1 (depth and breadth of marker genes across samples): the oracle restatement on a hand-computed case
-(CPU), the device path (sc_depth_scan: k_depth_fused) against the oracle on random records (-m gpu)."""
+(CPU), the device path (sc_depth_scan: k_depth_fused) against the oracle on random records (-m gpu).
+The kernel's named edge cases are in tests/depth_edge_lib.py (test_depth_edges_host.py, test_depth_edges_gpu.py)."""
 import os
 import random
 import sys
