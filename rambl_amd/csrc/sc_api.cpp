@@ -290,7 +290,7 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         std::memset(w.Rh, 0, sizeof(LevelResult));
         LevelBatch batch;
         batch.it[0] = w.level_item(jd_dev, H, KMAX);
-        const int kind = batch.it[0].kind & 0xFF;
+        const int kind = item_kind(batch.it[0].kind);
         launch_level_batch(st, kind, batch, 1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));

@@ -23,10 +23,14 @@
 
 namespace sc {
 
-// launchers defined in sc_kernels.hip
+// launchers defined in sc_graph_kernels.hip ...
 void launch_edge_support(hipStream_t st, const int* out_ptr, const int* out_node, const int* pool_ptr, const int* pool_rid,
                          const int* pool_cn, const uint8_t* node_is_end, const int* edge_src, int n_edges, int sorted,
                          int* support);
+void launch_msa(hipStream_t st, const MsaDev& d);
+void launch_thread(hipStream_t st, const ThreadDev& d, int* pool_sorted);
+int init_graph_kernels();
+// ... and in sc_level.hip
 bool level_wants_grid(const JobDev& job, const LevelHdr& h);
 int launch_level_grid(hipStream_t st, const JobDev& job, const LevelHdr& h, const LevelParams* Pd, LevelResult* R);
 int level_kind(const LevelHdr& h);
@@ -35,9 +39,9 @@ int level_table_capacity();
 void launch_level_batch(hipStream_t st, int kind, const LevelBatch& b, int n);
 void launch_level_any(hipStream_t st, const LevelBatch& b, int n);
 void launch_resident(hipStream_t st, const ResidentArgs& a, int slots);
-void launch_msa(hipStream_t st, const MsaDev& d);
-void launch_thread(hipStream_t st, const ThreadDev& d, int* pool_sorted);
-int init_kernels();
+int init_level_kernels();
+// the dynamic-LDS attributes of every kernel that needs one; nonzero: a HIP error
+inline int init_kernels() { return init_level_kernels() | init_graph_kernels(); }
 
 // ---------------------------------------------------------------------------
 struct Job {
@@ -259,7 +263,7 @@ struct Worker {
     JobDev job_dev(PinnedArena& ar, const FlatGraph& f, const std::vector<int>& ent_qoff, const std::vector<int>& mate_off,
                    const std::vector<int>& mate_idx, int n_reads, long qcap, int max_entries, long max_draws);
     LevelItem level_item(const JobDev* job, const LevelHdr& H, int K) const {
-        return LevelItem{job, H, level_kind(H) | (level_lds_kb(H, K) << 8), Pm, Rd};
+        return LevelItem{job, H, pack_kind(level_kind(H), level_lds_kb(H, K)), Pm, Rd};
     }
     void cluster(Job& job, const PoGraph& g, FlatGraph& f);
 };

@@ -1,8 +1,11 @@
 // Device-side data layout shared by the host driver (sc_sched.cpp, sc_region.cpp, sc_walk.cpp, sc_api.cpp) and the
-// HIP kernels (sc_kernels.hip).  All pointers are device pointers unless the
-// field name ends in _h (host-mapped pinned memory written/read by kernels).
+// HIP kernels of the graph stage and of the level walk (sc_graph_kernels.hip, sc_level.hip).  All pointers are device
+// pointers unless the field name ends in _h (host-mapped pinned memory written/read by kernels).
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
+#include <type_traits>
 
 namespace sc {
 
@@ -78,16 +81,41 @@ struct LevelParams {
     double lpt[MAXS * KK];       // log sub(a,b) - log comp(a): compact [S][K][K], K = JobDev::K
 };
 
+// The kind of a level names the kernel variant that serves it.  0: no sampler (k_level).  2 * NB - 1 + L, 1..16: the sampler
+// for NB = ceil(S / 16) = 1..8 register blocks per lane of a quad, L = 1 when its weight rows fit in LDS (0: they live in
+// HBM).  sc_stats::kind_levels counts levels by it.  This is the one place that knows the encoding.
+constexpr int N_SAMPLER_KINDS = 16;
+__host__ __device__ constexpr int sampler_kind(int nb, bool rows_lds) { return 2 * nb - 1 + (rows_lds ? 1 : 0); }
+__host__ __device__ constexpr bool kind_has_sampler(int kind) { return kind != 0; }
+__host__ __device__ constexpr int kind_nb(int kind) { return (kind + 1) / 2; }
+__host__ __device__ constexpr bool kind_rows_lds(int kind) { return kind % 2 == 0; }
+// LevelItem::kind carries the kind in its low byte and the LDS the level needs, in KB, above it
+__host__ __device__ constexpr int pack_kind(int kind, int lds_kb) { return kind | (lds_kb << 8); }
+__host__ __device__ constexpr int item_kind(int word) { return word & 0xFF; }
+__host__ __device__ constexpr int item_lds_kb(int word) { return (word >> 8) & 0xFFFF; }
+static_assert(sampler_kind(1, false) == 1 && sampler_kind(8, true) == N_SAMPLER_KINDS && kind_nb(sampler_kind(5, true)) == 5 &&
+              kind_rows_lds(sampler_kind(5, true)) && !kind_rows_lds(sampler_kind(5, false)) &&
+              item_kind(pack_kind(13, 157)) == 13 && item_lds_kb(pack_kind(13, 157)) == 157, "level kind");
+// A sampler kind as compile-time <NB, ROWS_LDS>: f(std::integral_constant<int, NB>, std::bool_constant<ROWS_LDS>) for the
+// variant `kind` names (a kind beyond the list gets the widest, NB = 8).  The one list of the sampler's variants.
+template <int NB = 1, class F>
+__host__ __device__ __forceinline__ void with_sampler_variant(int kind, F&& f) {
+    if constexpr (NB < 8) {
+        if (kind_nb(kind) != NB) { with_sampler_variant<NB + 1>(kind, f); return; }
+    }
+    if (kind_rows_lds(kind)) f(std::integral_constant<int, NB>{}, std::true_type{});
+    else f(std::integral_constant<int, NB>{}, std::false_type{});
+}
+
 // One launch serves the current level of up to MAXB regions: workgroup b takes batch.it[b].  What the level needs
 // to find its region travels in the kernel-argument segment: a pointer to the region's JobDev (device memory, filled
 // once per region, read through the constant address space), the level's scalars, the host-mapped parameter /
 // result blocks.  MAXB keeps the segment below 4 KB.
-struct LevelParams;
 struct LevelResult;
 struct LevelItem {
     const JobDev* job;           // device memory; constant while the region is walked
     LevelHdr h;
-    int kind;                    // level_kind(h): which variant of the level kernel serves it (k_level_any looks here)
+    int kind;                    // pack_kind(level_kind(h), level_lds_kb(h, K)): the variant of the level kernel that serves it, its LDS need
     const LevelParams* P;        // host-mapped
     LevelResult* R;              // host-mapped
 };
@@ -114,8 +142,6 @@ struct ResidentCtl {
     unsigned heartbeat;          // host: keeps changing while the context's server thread is alive
     unsigned pad[30];
 };
-struct LevelParams;
-struct LevelResult;
 struct ResidentArgs {
     Mailbox* mail;               // host-mapped, [slots]
     const ResidentCtl* ctl;      // host-mapped

@@ -5,7 +5,7 @@
 // canonise insertions/deletions, forward/backward merge, path collapse, level
 // numbering) with index-based storage, tombstoned deletion and linear-time pool
 // intersections, then flattens it into the level-major arrays the HIP clustering
-// kernels consume (sc_kernels.hip).  The insertion MSA (row a7) is delegated to
+// kernels consume (sc_graph_kernels.hip).  The insertion MSA (row a7) is delegated to
 // the device through `MsaFn`.
 #pragma once
 #include <cstdint>

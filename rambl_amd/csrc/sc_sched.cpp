@@ -143,14 +143,14 @@ void LevelServer::serve() {
             progressed = true;
         }
         if (progressed) { idle_spins = 0; continue; }
-        if ((idle_spins & 0xFFu) == 0) {
+        if (idle_spins % 256u == 0) {
             // idle: let the runtime retire finished launches of one free stream (it does so only when asked; left alone
             // they pile up for whoever synchronises the device next, ~10 us each)
             for (auto& ls : lstreams)
                 if (ls.busy == 0 && ls.unretired > 0) { if (hipStreamQuery(ls.s.st) == hipSuccess) ls.unretired = 0; break; }
         }
         __builtin_ia32_pause();
-        if ((++idle_spins & 0xFFFFFu) == 0) {
+        if (++idle_spins % (1u << 20) == 0) {
             // nothing has moved for a while: has a stream died under its batch, or drained without every stamp of it?
             for (size_t si = 0; si < lstreams.size(); si++) {
                 LaunchStream& ls = lstreams[si];
@@ -410,7 +410,7 @@ void Worker::complete_level(const LevelItem& it, bool timed) {
         if (alone) {
             for (unsigned spins = 0; __atomic_load_n(&Rh->seq, __ATOMIC_ACQUIRE) != want;) {
                 __builtin_ia32_pause();
-                if ((++spins & 0xFFFFFu) == 0)
+                if (++spins % (1u << 20) == 0)
                     if (const char* why = resident_failure(mb, &Rh->seq, want, t)) throw HipError(why);
             }
         } else {
@@ -427,7 +427,7 @@ void Worker::complete_level(const LevelItem& it, bool timed) {
         hipStream_t ls = ctx->launch->st;
         if (timed) HIPCHK(hipEventRecord(ev0, ls));
         (void)hipGetLastError();
-        launch_level_batch(ls, it.kind & 0xFF, batch, 1);
+        launch_level_batch(ls, item_kind(it.kind), batch, 1);
         { const hipError_t le = hipGetLastError(); if (le != hipSuccess) throw HipError(std::string("level kernel launch: ") + hipGetErrorString(le)); }
         if (timed) HIPCHK(hipEventRecord(ev1, ls));
         t_batch_launched = now_ms(); batch_n = 1;
@@ -444,7 +444,7 @@ void Worker::complete_level(const LevelItem& it, bool timed) {
         }
     } else {
         t_posted.store(now_ms(), std::memory_order_release);
-        ctx->server->submit(LevelRequest{this, it, it.kind & 0xFF, timed});
+        ctx->server->submit(LevelRequest{this, it, item_kind(it.kind), timed});
         wait_level();
     }
 }

@@ -160,8 +160,9 @@ struct LevelWalk {
             for (int i = 0; i < K * K; i++) m.sub[i] = 0;
             for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) m.sub[i * K + j] = (i == j) ? 100 * (1 - e) : 100 * e;
             recount(m);
-            m.dirty = 0xFFFFu;
-            for (int a = 0; a < KMAX; a++) m.stale[a] = 0xFFFFu;
+            constexpr unsigned all_symbols = (1u << KMAX) - 1u;
+            m.dirty = all_symbols;
+            for (int a = 0; a < KMAX; a++) m.stale[a] = (uint16_t)all_symbols;
             s.abundance = 0; s.slot = free_slots.back(); free_slots.pop_back();
             s.tail = -1; s.node = -1; s.hash = 1469598103934665603ull; s.seqlen = 0;
             level_strains.push_back(s);
@@ -351,7 +352,7 @@ struct LevelWalk {
             t_last_done = t_done;
         }
         stats.xcd_levels[Rh->xcc & 7]++;
-        stats.kind_levels[std::min(std::max(it.kind & 0xFF, 0), 16)]++;
+        stats.kind_levels[std::min(std::max(item_kind(it.kind), 0), N_SAMPLER_KINDS)]++;
     }
     // np_bayes_clustering, :128-244 (+ pruning :404-454)
     void np_bayes_clustering(int e0, int e1, int Q, bool has_dups, bool any_multi) {

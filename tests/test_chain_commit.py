@@ -1,4 +1,4 @@
-"""The commit section of the urn chain (rambl_amd/csrc/sc_kernels.hip, urn_chain_q): an accepted draw adds one to its
+"""The commit section of the urn chain (rambl_amd/csrc/sc_sampler.hpp, urn_chain_q): an accepted draw adds one to its
 strain's count in LDS and writes its strain as one byte to the region's draw log; the draws per (strain, read symbol)
 are counted from that log after the chain (draw_log_counts).  One sampler level through the production kernel
 (capi.Context.sample_level) against the oracle's draw loop, `kdraw` and `cnt` compared exactly, on the smallest shapes

@@ -699,3 +699,90 @@ def test_launch_per_level_path_with_many_regions_in_flight():
     tail = p.stdout.decode()[-1500:]
     assert p.returncode == 0, tail
     assert " passed" in tail and "failed" not in tail, tail
+
+
+# The grid path of a level (k_level_copy, k_level_update, k_level_has, k_hard_*) against the level's own workgroup on the
+# same input.  seed 2: paired reads (the mate loops); seed 5: insertions, so levels with multi-symbol labels stay in their
+# workgroup between levels on the grid; seed 7: noisy, up to five strains; tie525: tests/golden/tie_case525, whose outcome
+# rests on bitwise equal sums.
+_GRID_CASES = ["seed2", "seed5", "seed7", "tie525"]
+
+# argv: repository root, slots of the context, times the region is submitted, output prefix, then StrainCall's own argv.
+# Writes <prefix><i>.fa and <prefix><i>.trace (what SC_TRACE_FILE holds) for every submission i.
+_GRID_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+from rambl_amd import capi, cli
+slots, times, prefix = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
+pa = cli.parse_cmd_line(sys.argv[5:])
+regions = [(w, r) for w, r in cli.load_regions(pa) if len(r)]
+params = capi.default_params(float(pa.error_rate), float(pa.tau), float(pa.diff_rate), want_trace=True)
+with capi.Context(0, slots) as ctx:
+    hs = [[(w, ctx.submit(r, params)) for w, r in regions] for _ in range(times)]
+    for i, handles in enumerate(hs):
+        res = [(w, ctx.wait(h, want_trace=True)) for w, h in handles]
+        open("%s%d.fa" % (prefix, i), "w").write("".join(cli.format_fasta(w, r, pa.tau) for w, r in res))
+        open("%s%d.trace" % (prefix, i), "w").write("".join(r.trace for _, r in res))
+"""
+
+
+def _run_on_grid(args, d, slots=1, times=1):
+    """The region in a child process in which SC_GRID_MIN=0 sends every level the grid kernels can take to them (a hang or a
+    fault ends there, within the child's own time limit) -> [(FASTA, trace)] per submission."""
+    import subprocess
+    import sys
+    prefix = os.path.join(d, "grid")
+    env = dict(os.environ, SC_GRID_MIN="0")
+    p = subprocess.run([sys.executable, "-c", _GRID_CHILD, T.ROOT, str(slots), str(times), prefix] + list(args), env=env,
+                       timeout=300, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert p.returncode == 0, p.stdout.decode()[-2000:]
+    return [(open("%s%d.fa" % (prefix, i)).read(), open("%s%d.trace" % (prefix, i)).read()) for i in range(times)]
+
+
+@pytest.fixture(scope="module")
+def workgroup_runs(tmp_path_factory, oracle_bin):
+    """case -> (argv, expected FASTA, FASTA, trace) of this process, default thresholds: every level of these small regions
+    runs in its own workgroup.  Made once per case."""
+    made = {}
+
+    def get(case):
+        if case not in made:
+            d = str(tmp_path_factory.mktemp(case))
+            if case == "tie525":
+                args, _ = T.big_case(525, d)
+                exp_fa = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tie_case525", "expected.fa")).read()
+            else:
+                args = T.make_case(int(case[4:]), d)
+                exp_fa, _ = T.run_oracle(args, d)
+            tf = os.path.join(d, "workgroup.trace")
+            assert "SC_GRID_MIN" not in os.environ
+            got_fa = T.run_product(args, trace_file=tf)
+            made[case] = (args, exp_fa, got_fa, open(tf).read(), d)
+        return made[case]
+    return get
+
+
+@pytest.mark.parametrize("case", _GRID_CASES)
+def test_grid_path_equals_workgroup_path(case, workgroup_runs):
+    """Very large levels run their row copies, log-likelihood update, `has` marks and hard update on a grid; the claim is
+    that the grid computes bit for bit what the level's workgroup computes.  SC_GRID_MIN=0 (tests only) puts the thresholds
+    at zero, so these regions of tens to thousands of reads take the grid wherever it can serve (single-symbol labels, no
+    duplicate reads) and the workgroup elsewhere: FASTA equal to the expected one and to the workgroup run's, and the
+    per-level trace (abundances printed with 17 digits) byte-identical to the workgroup run's."""
+    args, exp_fa, wg_fa, wg_trace, d = workgroup_runs(case)
+    (grid_fa, grid_trace), = _run_on_grid(args, d)
+    assert wg_trace.count("\n") > 10
+    assert wg_fa == exp_fa
+    assert grid_fa == wg_fa
+    assert grid_trace == wg_trace
+
+
+def test_grid_path_in_front_of_resident_workers(workgroup_runs):
+    """The same for a resident workgroup that picks a level up behind the grid kernels: seed 7 twice in a two-slot context
+    under SC_GRID_MIN=0."""
+    args, exp_fa, wg_fa, wg_trace, d = workgroup_runs("seed7")
+    runs = _run_on_grid(args, d, slots=2, times=2)
+    assert wg_fa == exp_fa
+    for grid_fa, grid_trace in runs:
+        assert grid_fa == wg_fa
+        assert grid_trace == wg_trace

@@ -2,7 +2,7 @@
 entry sc_sample_level) on chosen inputs and CHOSEN UNIFORMS, compared with the oracle's draw loop (oracle_urn_draws,
 the loop of np_bayes_clustering in long double) for exact equality of the draws per strain and per (strain, symbol).
 
-The kernel decides a draw in one of three tiers (rambl_amd/csrc/sc_kernels.hip, urn_chain_q): a speculative fp32
+The kernel decides a draw in one of three tiers (rambl_amd/csrc/sc_sampler.hpp, urn_chain_q): a speculative fp32
 window with one-sided margins, an fp64 scan with a 1e-10 * T margin (slow_draw) and the literal evaluation of the
 reference's formula (exact_draw).  A wrong margin, lane or row index shows only when a uniform lands in the sliver it
 gets wrong, which seeded data practically never does.  So the uniforms here are placed at known distances from the

@@ -1,4 +1,4 @@
-"""CPU model of the sampler's window rule (rambl_amd/csrc/sc_kernels.hip, urn_chain_q): a draw evaluated in fp32
+"""CPU model of the sampler's window rule (rambl_amd/csrc/sc_sampler.hpp, urn_chain_q): a draw evaluated in fp32
 with the counts in front of the window, p draws earlier, is final when no boundary above the target u*T lies within
 eps*T + u*p of it and none below it within eps*T + (1-u)*p: each earlier draw adds L <= 1 to one count, which moves
 cum_s - u*T up by at most (1-u) and down by at most u.  The model runs that rule with numpy fp32 arithmetic next to

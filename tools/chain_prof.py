@@ -2,7 +2,7 @@
 """Cycles of a pass of the urn chain by section, one region of the configs[1] shape (a launch per level).
 
 Needs the experiment build of the library (`make -C rambl_amd/csrc clean && make -C rambl_amd/csrc EXTRA=-DSC_CHAIN_PROF`),
-which stamps the shader clock on wavefront 0 between the sections of every pass (sc_kernels.hip, CHAIN_STAMP) and exports
+which stamps the shader clock on wavefront 0 between the sections of every pass (sc_sampler.hpp, CHAIN_STAMP) and exports
 `sc_debug_chain_prof`.  A stamp costs about 50 cycles, which stay in the section in front of it.  The three stamps inside
 the commit section wait for the LDS operations in front of them, so what the product build leaves in flight (the next
 rows' LDS reads, the count's atomic) is charged to its own part here.
