@@ -379,6 +379,52 @@ int sc_profile_counts(int device, const char* gene_text, const long* gene_off, i
 /* E6 of a segment of L bases with doubled raw score score2 against gene_bases gene bases; no device is touched. */
 double sc_profile_evalue6(int L, long gene_bases, int score2, double ka_lambda, double ka_k);
 
+/* ---- genus assignment of gene sequences on the device (rambl_amd/csrc/sc_taxa.hip) ---------------
+ *
+ * scripts/per_sample_gene_profile_fast.py:223-246 and scripts/per_sample_taxon_profile.py:47-52 run the RDP classifier, a
+ * Java program, on the assembled genes.  These entry points compute RDP's stated rule instead -- naive Bayes over 8-mers
+ * with bootstrap trials -- under a contract of this project's own: parity with RDP's output is not claimed.
+ *   words     2 bits per base (A C G T/U = 0 1 2 3, either case), first base most significant; a window with any other
+ *             character is no word; a sequence's word list is its words in order, repeats included
+ *   training  n(w), m_g(w): the sequences (of genus g) that hold w; P_w = (n(w) + 0.5) / (N + 1),
+ *             P(w|g) = (m_g(w) + P_w) / (M_g + 1), cell q[w * G + g] = llrint(log2(P(w|g)) * 1024) computed in fp64
+ *   score     the sum of q over a query's word list (forward strand only); the largest wins, the lowest genus on a tie
+ *   trials    trial t draws D = max(W / 8, 5) positions of the W-word list, draw j at (hi32(z) * W) >> 32 with
+ *             z = splitmix64's finaliser of (seed ^ key) + (t * 65536 + j + 1) * 0x9E3779B97F4A7C15; key is per query
+ * Limits: 1..16384 genera, 1..2^24 training sequences of at most 2^24 bases and 2^32 in all, queries of 1..8192 bases,
+ * 1..1024 trials;
+ * outside them SC_ERR_UNSUPPORTED.  The message of the calling thread's last failure is in sc_taxa_error().
+ * grid_cap bounds the blocks of every launch of a call (0: the library's own bound). */
+typedef struct sc_taxa_model sc_taxa_model;
+typedef struct sc_taxa_stats {
+    double upload_ms;      /* HIP events: sequences (train) or word lists and keys (classify) to the device */
+    double words_ms;       /* HIP events: k_taxa_words (train only) */
+    double table_ms;       /* HIP events: k_taxa_table (train only) */
+    double score_ms;       /* HIP events: k_taxa_score and k_taxa_pick (classify only) */
+    double total_ms;       /* wall time of the call, host packing included */
+    long n_seqs;           /* training sequences, or queries */
+    long n_words;          /* train: distinct (sequence, word) pairs counted; classify: words of all queries' lists */
+    long n_genera;
+    long table_bytes;      /* the model's table on the device: 65536 * n_genera * 4 */
+} sc_taxa_stats;
+/* seq_genus[n_seqs]: the genus index (0..n_genera-1) of every training sequence; a genus may have none.  keep_counts not 0:
+ * the model also keeps m as it stood before it became the table (as much memory again), for sc_taxa_model_counts. */
+int sc_taxa_train(int device, const char* seq_text, const long* seq_off, int n_seqs, const int* seq_genus, int n_genera, int grid_cap,
+                  int keep_counts, sc_taxa_model** model, sc_taxa_stats* stats);
+/* Out per query: best_genus (-1 for a query without a word: it has no trials either), trial_winner[n_queries * n_trials],
+ * n_words (W). */
+int sc_taxa_classify(const sc_taxa_model* model, const char* query_text, const long* query_off, int n_queries,
+                     const unsigned long long* query_key, unsigned long long seed, int n_trials, int grid_cap, int* best_genus,
+                     int* trial_winner, int* n_words, sc_taxa_stats* stats);
+/* Read-backs for tests and diagnostics, 65536 values each: a genus' m with the model's n (SC_ERR_UNSUPPORTED unless the
+ * model was trained with keep_counts: the table replaces m in place), and its column of the table. */
+int sc_taxa_model_counts(const sc_taxa_model* model, int genus, unsigned* m_out, unsigned* n_out);
+int sc_taxa_model_table(const sc_taxa_model* model, int genus, int* q_out);
+void sc_taxa_free(sc_taxa_model* model);
+const char* sc_taxa_error(void);
+/* The word-list position of draw `draw` of trial `trial` for a list of W words (-1 when W < 1); no device is touched. */
+long sc_taxa_draw(unsigned long long seed, unsigned long long key, int trial, int draw, int W);
+
 #ifdef __cplusplus
 }
 #endif

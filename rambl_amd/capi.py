@@ -63,6 +63,14 @@ class ScProfileCountStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScTaxaStats(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("words_ms", C.c_double), ("table_ms", C.c_double), ("score_ms", C.c_double), ("total_ms", C.c_double),
+                ("n_seqs", C.c_long), ("n_words", C.c_long), ("n_genera", C.c_long), ("table_bytes", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StrainCallError(RuntimeError):
     def __init__(self, code, msg=""):
         super().__init__("%s (%d)%s" % (ERRORS.get(code, "error"), code, (": " + msg) if msg else ""))
@@ -132,6 +140,19 @@ def load_library():
                                       C.c_int, C.c_long, ip, ip, ip, lp, C.c_long, lp, C.POINTER(ScProfileCountStats)]
     lib.sc_profile_evalue6.argtypes = [C.c_int, C.c_long, C.c_int, C.c_double, C.c_double]
     lib.sc_profile_evalue6.restype = C.c_double
+    u64, u64p = C.c_ulonglong, C.POINTER(C.c_ulonglong)
+    lib.sc_taxa_train.argtypes = [C.c_int, cp, lp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(ScTaxaStats)]
+    lib.sc_taxa_classify.argtypes = [vp, cp, lp, C.c_int, u64p, u64, C.c_int, C.c_int, ip, ip, ip, C.POINTER(ScTaxaStats)]
+    lib.sc_taxa_model_counts.argtypes = [vp, C.c_int, up, up]
+    lib.sc_taxa_model_table.argtypes = [vp, C.c_int, ip]
+    lib.sc_taxa_free.argtypes = [vp]
+    lib.sc_taxa_free.restype = None
+    lib.sc_taxa_error.argtypes = []
+    lib.sc_taxa_error.restype = cp
+    lib.sc_taxa_draw.argtypes = [u64, u64, C.c_int, C.c_int, C.c_int]
+    lib.sc_taxa_draw.restype = C.c_long
+    for f in ("sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table"):
+        getattr(lib, f).restype = C.c_int
     for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads", "sc_profile_hits",
               "sc_profile_hits_seeded", "sc_profile_seed_length", "sc_profile_counts"):
         getattr(lib, f).restype = C.c_int
@@ -146,7 +167,8 @@ EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "
            "sc_roi_thread_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
            "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
            "sc_align_error", "sc_profile_hits", "sc_profile_error", "sc_profile_hits_seeded", "sc_profile_seed_length",
-           "sc_profile_counts"]         # (sc_profile_evalue6 as well: load_library looks it up itself; the list holds letter-only names)
+           "sc_profile_counts", "sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table", "sc_taxa_free", "sc_taxa_error",
+           "sc_taxa_draw"]              # (sc_profile_evalue6 as well: load_library looks it up itself; the list holds letter-only names)
 
 
 def default_params(error_rate=0.01, tau=0.02, diff_rate=0.01, graph_only=False, want_trace=False, want_timing=False, want_graph=False):
@@ -672,3 +694,94 @@ def profile_counts(genes, segs, seg_read, min_identity=95.0, max_evalue=1e-10, k
             raise StrainCallError(rc, lib().sc_profile_error().decode())
         k = n.value
         return ProfileCounts([(int(gene[i]), int(times[i]), int(share[i]), int(n_behind[i])) for i in range(k)], st)
+
+
+TAXA_WORDS = 65536
+TAXA_TRIALS = 100
+
+
+def taxa_draw(seed, key, trial, draw, n_words):
+    """sc_taxa_draw (host only): the word-list position of draw `draw` of trial `trial` for a list of n_words words."""
+    return int(lib().sc_taxa_draw(int(seed), int(key), int(trial), int(draw), int(n_words)))
+
+
+def _pack_long(seqs):
+    import numpy as np
+    return b"".join(seqs), np.array([0] + [len(x) for x in seqs], dtype=np.int64).cumsum()
+
+
+class TaxaModel:
+    """A model trained by sc_taxa_train, held on one device until close().  seqs: the training sequences
+    (bytes), genus: one genus index in 0..n_genera-1 per sequence.  grid_cap bounds the blocks of every launch (0: the
+    library's own bound); keep_counts: also keep m for counts(), as much device memory again; stats is the ScTaxaStats of the
+    training."""
+
+    def __init__(self, seqs, genus, n_genera, device=0, grid_cap=0, keep_counts=False):
+        import numpy as np
+        if len(genus) != len(seqs):
+            raise ValueError("%d genus indices for %d sequences" % (len(genus), len(seqs)))
+        text, off = _pack_long(seqs)
+        gi = np.ascontiguousarray(genus, dtype=np.int32)
+        self.n_genera = int(n_genera)
+        self._h = C.c_void_p()
+        self.stats = ScTaxaStats()
+        rc = lib().sc_taxa_train(int(device), text, off.ctypes.data_as(C.POINTER(C.c_long)), len(seqs), gi.ctypes.data_as(C.POINTER(C.c_int)),
+                                 self.n_genera, int(grid_cap), int(bool(keep_counts)), C.byref(self._h), C.byref(self.stats))
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_taxa_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().sc_taxa_free(self._h)
+            except TypeError:          # interpreter shutdown
+                pass
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def classify(self, queries, keys, seed=0, n_trials=TAXA_TRIALS, grid_cap=0):
+        """sc_taxa_classify: queries (bytes) with one 64-bit key each.  Returns (best_genus[n], trial_winner[n][n_trials],
+        n_words[n], ScTaxaStats); a query without a word has -1 in the first two."""
+        import numpy as np
+        n = len(queries)
+        if len(keys) != n:
+            raise ValueError("%d keys for %d queries" % (len(keys), n))
+        text, off = _pack_long(queries)
+        key = np.ascontiguousarray(keys, dtype=np.uint64)
+        best, words = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        winner = np.zeros((max(n, 1), max(int(n_trials), 1)), dtype=np.int32)
+        st = ScTaxaStats()
+        ip = C.POINTER(C.c_int)
+        rc = lib().sc_taxa_classify(self._h, text, off.ctypes.data_as(C.POINTER(C.c_long)), n, key.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                    int(seed), int(n_trials), int(grid_cap), best.ctypes.data_as(ip), winner.ctypes.data_as(ip),
+                                    words.ctypes.data_as(ip), C.byref(st))
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_taxa_error().decode())
+        return best[:n], winner[:n], words[:n], st
+
+    def counts(self, genus):
+        """sc_taxa_model_counts: (m of the genus, n), 65 536 uint32 each; of a model trained with keep_counts."""
+        import numpy as np
+        m, n = np.zeros(TAXA_WORDS, dtype=np.uint32), np.zeros(TAXA_WORDS, dtype=np.uint32)
+        up = C.POINTER(C.c_uint)
+        rc = lib().sc_taxa_model_counts(self._h, int(genus), m.ctypes.data_as(up), n.ctypes.data_as(up))
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_taxa_error().decode())
+        return m, n
+
+    def table(self, genus):
+        """sc_taxa_model_table: the genus' column of the table, 65 536 int32."""
+        import numpy as np
+        q = np.zeros(TAXA_WORDS, dtype=np.int32)
+        rc = lib().sc_taxa_model_table(self._h, int(genus), q.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_taxa_error().decode())
+        return q

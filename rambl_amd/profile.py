@@ -1,12 +1,14 @@
 """After the assembly: how much of each assembled gene is in one sample, on one MI355X GPU.
 
-Mirror of scripts/per_sample_gene_profile_fast.py with `-n` (no copy-number correction): the reads the sample's
+Mirror of scripts/per_sample_gene_profile_fast.py (copy-number correction from a fixrank file of taxa.py, off by default
+as with `-n`): the reads the sample's
 alignment file mapped are extracted (extract_mapped_reads.cpp:29-105), searched in the assembled genes
 (`makeblastdb` / `blastn -reward 1 -penalty -2`, :80-117), the hits turned into a CSV (`bigBlastParser` + `sqlite3`,
 :120-153), counted (blastout2abundance.cpp:70-196) and written as `<sample>_gene_count.tsv` (:324-336).  blastn and the
 tools around it are replaced by the exact optimum of blastn's scoring with a fixed tie-break, computed by
 sc_profile_hits (rambl_amd/csrc/sc_profile.hip); the counting rule is the reference's, on the host, one pass over the hits.
 With --counts the rule runs on the device over each read's best hits only (sc_profile_counts).
+--copy-correct divides every count by its gene's copy number (copy_number_correct, :223-246).
 """
 import decimal
 import math
@@ -158,16 +160,28 @@ def format_table(sample, counts, relative=False):
 
 
 def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=MAX_EVALUE, relative=False, ka_lambda=KA_LAMBDA,
-                 ka_k=KA_K, out_dir=".", device=0, keep_hits=False, verbose=False, seeded=False, counts_only=False):
+                 ka_k=KA_K, out_dir=".", device=0, keep_hits=False, verbose=False, seeded=False, counts_only=False, copy_correct=None):
     """per_sample_gene_profile (:253-279) and the table of main (:324-336) for one sample.  Writes
     <out_dir>/<sample>_gene_count.tsv (and <sample>_hits.csv with `keep_hits`); returns the table path and the
     sc_profile_stats of the device call(s).  seeded: only the (segment, gene) pairs that share a k-mer are scored
     (sc_profile_hits_seeded): the same hits, the same files.  counts_only: the table comes from
     sc_profile_counts, which picks, traces and counts only each read's best hits on the device: the same
-    table, no hit list (so no `keep_hits`); the statistics are sc_profile_count_stats."""
+    table, no hit list (so no `keep_hits`); the statistics are sc_profile_count_stats.  copy_correct: None, or (fixrank path,
+    copy-number table path, threshold): every count is divided by its gene's copy number before it is rounded
+    (copy_number_correct, :223-246; the fixrank file comes from `rambl-taxa classify`)."""
     if counts_only and keep_hits:
         raise ValueError("there is no hit list in the counts mode")
     from . import samio
+
+    correction = None
+    if copy_correct is not None:                                # read before the device's work: a mistyped path fails at once
+        from . import taxa
+        with open(copy_correct[0]) as f:
+            correction = (taxa.parse_fixrank(f.read()), taxa.load_copy_numbers(copy_correct[1]), copy_correct[2])
+
+    def corrected(counts):
+        return counts if correction is None else taxa.correct_counts(counts, *correction)
+
     fa = samio.Fasta(fasta)
     if not fa.order:
         raise ValueError("%s holds no gene" % fasta)
@@ -182,7 +196,7 @@ def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=
     if counts_only:
         seg_read, n_reads = read_index([q.decode() for q, _ in segments])
         res = capi.profile_counts(genes, [s for _, s in segments], seg_read, min_identity, max_evalue, ka_lambda, ka_k, device, seeded=seeded)
-        counts = counts_from_triples(res.triples, fa.order)
+        counts = corrected(counts_from_triples(res.triples, fa.order))
         with open(path, "w") as f:
             f.write(format_table(sample, counts, relative))
         if verbose:
@@ -194,7 +208,7 @@ def gene_profile(fasta, aln_path, sample, min_identity=MIN_IDENTITY, max_evalue=
         return path, res.stats
     hits = capi.profile_hits(genes, [s for _, s in segments], min_identity, max_evalue, ka_lambda, ka_k, device, seeded=seeded)
     rows = hit_rows(hits, [q.decode() for q, _ in segments], [len(s) for _, s in segments], fa.order)
-    counts = raw_abundance(rows, min_identity, max_evalue)
+    counts = corrected(raw_abundance(rows, min_identity, max_evalue))
     if keep_hits:
         with open(os.path.join(out_dir, sample + "_hits.csv"), "w") as f:
             f.write(hits_csv(rows))
@@ -230,9 +244,13 @@ def main(argv=None):
     ap.add_argument("-A", "--max_num_alignments", dest="max_num_align", type=int, default=30, help="only 30: no cap is applied")
     ap.add_argument("-I", "--max_identity", dest="max_align_iden", type=float, default=MIN_IDENTITY, help="least alignment identity in percent [95]")
     ap.add_argument("-n", "--ignore-copy-correct", dest="ignore_copy_correct", action="store_true",
-                    help="no copy number correction (always: the correction needs the RDP classifier and is not built)")
+                    help="no copy number correction (the default; --copy-correct turns it on)")
     ap.add_argument("-C", "--rdp-classifier", dest="rdp_classifier", default=None, help="not available")
     ap.add_argument("-t", "--thresh", dest="thresh", type=float, default=None, help="not available")
+    ap.add_argument("--copy-correct", dest="copy_correct", default=None, metavar="FIXRANK",
+                    help="divide every gene's count by its copy number: the genes' fixrank file from `rambl-taxa classify` (needs --copy-number)")
+    ap.add_argument("--copy-number", dest="copy_number", default=None, metavar="TSV", help="copy numbers per taxon: columns `name` and `mean` (rrnDB)")
+    ap.add_argument("--copy-thresh", dest="copy_thresh", type=float, default=None, help="least bootstrap confidence of a rank that corrects [0.6]")
     ap.add_argument("-r", "--rel", dest="relative_abundance", action="store_true", help="output relative abundance")
     ap.add_argument("--ka-lambda", dest="ka_lambda", type=float, default=KA_LAMBDA, help="Karlin-Altschul lambda [%g]" % KA_LAMBDA)
     ap.add_argument("--ka-k", dest="ka_k", type=float, default=KA_K, help="Karlin-Altschul K [%g]" % KA_K)
@@ -247,6 +265,12 @@ def main(argv=None):
     logging.basicConfig(format="[%(asctime)s] %(levelname)s : %(message)s", level=logging.INFO)
     if a.rdp_classifier is not None or a.thresh is not None:
         ap.error("copy number correction (-C / -t) needs the RDP classifier and is not built: the tool behaves as the script does with -n")
+    if (a.copy_correct is None) != (a.copy_number is None):
+        ap.error("--copy-correct FIXRANK and --copy-number TSV go together")
+    if a.copy_thresh is not None and a.copy_correct is None:
+        ap.error("--copy-thresh needs --copy-correct")
+    if a.copy_correct is not None and a.ignore_copy_correct:
+        ap.error("--copy-correct cannot be combined with -n")
     if a.counts and a.keep_hits:
         ap.error("--counts cannot be combined with --keep-hits: there is no hit list in this mode")
     given = {"word_size": a.word_size, "reward": a.reward, "penalty": a.penalty, "max_num_align": a.max_num_align}
@@ -255,7 +279,8 @@ def main(argv=None):
                  "without word seeding or a cap on alignments (got -w %d -R %d -P %d -A %d)" % (a.word_size, a.reward, a.penalty, a.max_num_align))
     os.environ["SC_INGEST_THREADS"] = str(max(1, min(a.cores, capi.host_plan(1)[2])))
     gene_profile(a.fasta, a.bam, a.sample, a.max_align_iden, a.e_value, a.relative_abundance, a.ka_lambda, a.ka_k, a.out_dir, a.device,
-                 a.keep_hits, a.verbose, a.seeded, a.counts)
+                 a.keep_hits, a.verbose, a.seeded, a.counts,
+                 None if a.copy_correct is None else (a.copy_correct, a.copy_number, 0.6 if a.copy_thresh is None else a.copy_thresh))
     return 0
 
 
