@@ -159,6 +159,23 @@ int sc_roi_edge_support(sc_ctx* ctx, int handle, int* support, int cap, int* n_e
 int sc_roi_thread_tables(sc_ctx* ctx, int handle, int* count, int* first_read, int cls_cap, int* pool, long pool_cap,
                          char* symbols, int* n_cls, long* n_pool);
 
+/* The other three tables of row a5, for tests: which read adds each edge, as the threading kernels return them before
+ * the host stitches nodes and edges from them.  smin[i*8+c] = the first read whose first CIGAR operation is M and whose
+ * first base lands in class (i, c); emin[i*8+c] = the first read whose last operation is M and whose last base lands
+ * there; tmin[i*64 + cp*8 + c] = the first read with symbols cp, c on window positions i-1, i inside one M run or across two
+ * adjacent M operations.  Absent entries are INT_MAX.  smin and emin hold *n_cls = glen*8 values, tmin 8 * *n_cls; kept for
+ * a region submitted with graph_only or want_graph, as the tables of sc_roi_thread_tables are. */
+int sc_roi_thread_edges(sc_ctx* ctx, int handle, int* smin, int* emin, int* tmin, int cls_cap, int* n_cls);
+
+/* Row a16 on raw arrays, for tests: the edge-support kernel on a graph the caller states as CSR pools
+ * (pool_ptr[n_nodes+1], pool_rid, pool_cn: the reads of every node with their copy numbers), node_is_end[n_nodes] and the
+ * edges (edge_src[e] -> edge_dst[e]); node 0 is the source.  sorted = 1 promises pools in ascending read order (checked:
+ * SC_ERR_ARG otherwise) and takes the kernel's binary searches, sorted = 0 its linear count.  support_out[n_edges].
+ * Uploads, launches and copies back; nothing else. */
+int sc_edge_support_tables(sc_ctx* ctx, int n_nodes, const int* pool_ptr, const int* pool_rid, const int* pool_cn,
+                           const unsigned char* node_is_end, int n_edges, const int* edge_src, const int* edge_dst, int sorted,
+                           int* support_out);
+
 /* Row a14 on its own, for tests: one sampler level (the Polya-urn draws of np_bayes_clustering,
  * NonparametricClustering.cpp:230-249) through the production level kernel, on chosen inputs and
  * chosen uniforms.  S (2..128) strains with urn weights a0[S] and read log-likelihood rows

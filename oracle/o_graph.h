@@ -745,6 +745,21 @@ static void output_edge(Graph *g, FILE *f) {
         for (int k = 0; k < x->pool.n; k++) rc += x->pool.v[k].cn;
         fprintf(f, "#\t%d\t%d\t%s\t%d\n", x->id, x->level, x->lab, rc);
     }
+    /* SC_ORACLE_DUMP_POOLS=<path>: the read pool of every node as "id<TAB>rid:cn ..." lines, for tests that restate
+       number_of_reads_cover_nodes over the pools themselves (the -G text holds only their sums) */
+    if (getenv("SC_ORACLE_DUMP_POOLS")) {
+        FILE *pf = fopen(getenv("SC_ORACLE_DUMP_POOLS"), "a");
+        if (pf) {
+            fprintf(pf, "graph\t%d\n", g->nodes.n);
+            for (int i = 0; i < g->nodes.n; i++) {
+                Node *x = g->nodes.v[i];
+                fprintf(pf, "%d\t", x->id);
+                for (int k = 0; k < x->pool.n; k++) fprintf(pf, "%s%d:%d", k ? " " : "", x->pool.v[k].rid, x->pool.v[k].cn);
+                fprintf(pf, "\n");
+            }
+            fclose(pf);
+        }
+    }
     for (int i = 0; i < g->nodes.n; i++) {
         Node *x = g->nodes.v[i];
         for (int k = 0; k < x->out.n; k++)

@@ -104,6 +104,8 @@ def load_library():
     lib.sc_roi_edge_support.argtypes = [vp, C.c_int, ip, C.c_int, ip]
     lib.sc_msa_align.argtypes = [vp, cp, ip, C.c_int, C.c_char_p, C.c_long, ip]
     lib.sc_roi_thread_tables.argtypes = [vp, C.c_int, ip, ip, C.c_int, ip, C.c_long, C.c_char_p, ip, C.POINTER(C.c_long)]
+    lib.sc_roi_thread_edges.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, ip]
+    lib.sc_edge_support_tables.argtypes = [vp, C.c_int, ip, ip, ip, C.POINTER(C.c_ubyte), C.c_int, ip, ip, C.c_int, ip]
     dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint)
     lib.sc_sample_level.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.POINTER(C.c_ubyte), C.c_int, C.c_int, ip, ip, ip, ip, ip,
                                     C.c_int, dp, C.c_int, up, up, C.POINTER(C.c_long)]
@@ -157,14 +159,14 @@ def load_library():
               "sc_profile_hits_seeded", "sc_profile_seed_length", "sc_profile_counts"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
-              "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level"):
+              "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level", "sc_roi_thread_edges", "sc_edge_support_tables"):
         getattr(lib, f).restype = C.c_int
     return lib
 
 
 EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "sc_host_plan", "sc_host_bind", "sc_roi_submit", "sc_roi_wait", "sc_roi_result",
            "sc_roi_graph_dump", "sc_roi_trace", "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align",
-           "sc_roi_thread_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
+           "sc_roi_thread_tables", "sc_roi_thread_edges", "sc_edge_support_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
            "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
            "sc_align_error", "sc_profile_hits", "sc_profile_error", "sc_profile_hits_seeded", "sc_profile_seed_length",
            "sc_profile_counts", "sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table", "sc_taxa_free", "sc_taxa_error",
@@ -484,6 +486,33 @@ class Context:
         if rc != SC_OK:
             raise self._err(rc)
         return list(cnt[:ncls.value]), list(first[:ncls.value]), list(pool[:npool.value]), sym.raw
+
+    def thread_edges(self, handle):
+        """Row a5, a test entry: (smin[glen*8], emin[glen*8], tmin[glen*64]) of a finished region; absent entries INT_MAX."""
+        ncls = C.c_int()
+        self.lib.sc_roi_thread_edges(self.h, handle, None, None, None, 0, C.byref(ncls))
+        n = ncls.value
+        smin, emin, tmin = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(8 * n, 1))()
+        rc = self.lib.sc_roi_thread_edges(self.h, handle, smin, emin, tmin, n, C.byref(ncls))
+        if rc != SC_OK:
+            raise self._err(rc)
+        return list(smin[:n]), list(emin[:n]), list(tmin[:8 * n])
+
+    def edge_support_tables(self, pool_ptr, pool_rid, pool_cn, node_is_end, edge_src, edge_dst, sorted_pools):
+        """Row a16 on raw arrays, a test entry: the support of every edge (edge_src[e] -> edge_dst[e])."""
+        import numpy as np
+        ptr_, rid, cn, src, dst = (np.ascontiguousarray(x, dtype=np.int32) for x in (pool_ptr, pool_rid, pool_cn, edge_src, edge_dst))
+        end = np.ascontiguousarray(node_is_end, dtype=np.uint8)
+        assert rid.shape == cn.shape and src.shape == dst.shape and ptr_.size == end.size + 1
+        out = np.zeros(max(src.size, 1), dtype=np.int32)
+
+        def ptr(x):
+            return x.ctypes.data_as(C.POINTER(C.c_ubyte if x.dtype == np.uint8 else C.c_int))
+        rc = self.lib.sc_edge_support_tables(self.h, end.size, ptr(ptr_), ptr(rid), ptr(cn), ptr(end), src.size, ptr(src), ptr(dst),
+                                             int(sorted_pools), ptr(out))
+        if rc != SC_OK:
+            raise self._err(rc)
+        return out[:src.size].tolist()
 
     def sample_level(self, a0, ll, has, ent_rid, ent_cn, ent_sym, mates, n_sweeps, U, e0=1):
         """Row a14 on its own (a test entry): one sampler level through the production kernel with the uniforms `U`.

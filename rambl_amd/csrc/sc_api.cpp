@@ -219,6 +219,56 @@ int sc_roi_thread_tables(sc_ctx* h, int handle, int* count, int* first_read, int
     std::memcpy(symbols, job->thr_sym.data(), std::min<size_t>(8, job->thr_sym.size()));
     return SC_OK;
 }
+int sc_roi_thread_edges(sc_ctx* h, int handle, int* smin, int* emin, int* tmin, int cls_cap, int* n_cls) {
+    if (!h || !n_cls) return SC_ERR_ARG;
+    auto job = find_job(h, handle);
+    if (!job || job->status != 1) return SC_ERR_ARG;
+    *n_cls = (int)job->thr_smin.size();
+    if (!smin || !emin || !tmin || cls_cap < *n_cls) return SC_ERR_CAPACITY;
+    std::memcpy(smin, job->thr_smin.data(), sizeof(int) * job->thr_smin.size());
+    std::memcpy(emin, job->thr_emin.data(), sizeof(int) * job->thr_emin.size());
+    std::memcpy(tmin, job->thr_tmin.data(), sizeof(int) * job->thr_tmin.size());
+    return SC_OK;
+}
+int sc_edge_support_tables(sc_ctx* h, int n_nodes, const int* pool_ptr, const int* pool_rid, const int* pool_cn,
+                           const unsigned char* node_is_end, int n_edges, const int* edge_src, const int* edge_dst, int sorted,
+                           int* support_out) {
+    if (!h || n_nodes < 1 || n_edges < 0 || !pool_ptr || !node_is_end || (sorted != 0 && sorted != 1)) return SC_ERR_ARG;
+    if (n_edges > 0 && (!edge_src || !edge_dst || !support_out)) return SC_ERR_ARG;
+    if (pool_ptr[0] != 0) return SC_ERR_ARG;
+    for (int a = 0; a < n_nodes; a++) if (pool_ptr[a + 1] < pool_ptr[a]) return SC_ERR_ARG;
+    const int np = pool_ptr[n_nodes];
+    if (np > 0 && (!pool_rid || !pool_cn)) return SC_ERR_ARG;
+    for (int e = 0; e < n_edges; e++)
+        if (edge_src[e] < 0 || edge_src[e] >= n_nodes || edge_dst[e] < 0 || edge_dst[e] >= n_nodes) return SC_ERR_ARG;
+    if (sorted)                                        // the binary searches of k_edge_support need what the flag promises
+        for (int a = 0; a < n_nodes; a++)
+            for (int x = pool_ptr[a] + 1; x < pool_ptr[a + 1]; x++) if (pool_rid[x] < pool_rid[x - 1]) return SC_ERR_ARG;
+    if (n_edges == 0) return SC_OK;
+    Ctx* ctx = &h->c;
+    try {
+        Worker w;                                      // a private worker: own stream
+        w.init_private(ctx);
+        const hipStream_t st = w.st;
+        const std::vector<int> pptr(pool_ptr, pool_ptr + n_nodes + 1), prid(pool_rid, pool_rid + np), pcn(pool_cn, pool_cn + np);
+        const std::vector<int> esrc(edge_src, edge_src + n_edges), edst(edge_dst, edge_dst + n_edges);
+        const std::vector<uint8_t> isend(node_is_end, node_is_end + n_nodes);
+        DevBuf b_ptr, b_rid, b_cn, b_end, b_src, b_dst, b_sup;
+        const int* d_ptr = upload(w.passthrough, b_ptr, pptr, st);
+        const int* d_rid = upload(w.passthrough, b_rid, prid, st);
+        const int* d_cn = upload(w.passthrough, b_cn, pcn, st);
+        const uint8_t* d_end = upload(w.passthrough, b_end, isend, st);
+        const int* d_src = upload(w.passthrough, b_src, esrc, st);
+        const int* d_dst = upload(w.passthrough, b_dst, edst, st);
+        int* d_sup = (int*)b_sup.ensure(sizeof(int) * (size_t)n_edges);
+        launch_edge_support(st, nullptr, d_dst, d_ptr, d_rid, d_cn, d_end, d_src, n_edges, sorted, d_sup);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(support_out, d_sup, sizeof(int) * (size_t)n_edges, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return SC_OK;
+    } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
+    catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
+}
 int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const double* ll, const unsigned char* has, int n_ent,
                     int e0, const int* ent_rid, const int* ent_cn, const int* ent_sym, const int* mate_off, const int* mate_idx,
                     int n_sweeps, const double* U, int n_u, unsigned* kdraw, unsigned* cnt, long* out) {

@@ -57,6 +57,7 @@ struct Job {
     std::string graph_dump, trace;
     std::vector<int> edge_support;
     std::vector<int> thr_count, thr_first, thr_pool;
+    std::vector<int> thr_smin, thr_emin, thr_tmin;   // kept with thr_count, for sc_roi_thread_edges
     std::string thr_sym;
     sc_stats stats{};
     double t_submit = 0;

@@ -290,8 +290,9 @@ void Worker::process(Job& job) {
     ThreadFn thr = [this, &job](const std::string& G, const std::vector<AlignedRead>& R, const std::vector<std::vector<CigarOp>>& cg,
                           ThreadTables& T) {
         thread_device(G, R, cg, T);
-        if (job.params.graph_only || job.params.want_graph) {      // kept for sc_roi_thread_tables
+        if (job.params.graph_only || job.params.want_graph) {      // kept for sc_roi_thread_tables / sc_roi_thread_edges
             job.thr_count = T.count; job.thr_first = T.minrid; job.thr_pool = T.pool; job.thr_sym.assign(T.sym.begin(), T.sym.end());
+            job.thr_smin = T.smin; job.thr_emin = T.emin; job.thr_tmin = T.tmin;                 // for sc_roi_thread_edges
         }
     };
     // a context with one region in flight gives the region's bulk copies (class pools, flattening: 88 M entries on the

@@ -6,10 +6,11 @@ FASTA + SAM), then stdout FASTA, `-G` graph dump and the 17-digit per-level trac
 of oracle/_ref/StrainCall_ref (the reference sources compiled by oracle/Makefile),
 cross-checked byte for byte against the shipped binary
 /root/reference/StrainCall/StrainCall for FASTA and graph.  The MSA vectors come
-from oracle/_ref/msa_ref (the reference's MultipleSequenceAlignmentSP::align).
+from oracle/_ref/msa_ref (the reference's MultipleSequenceAlignmentSP::align): 120 seeded ones, then the named cases of
+tests/graph_edge_lib.py (each with its "name").
 Only inputs' digests and expected outputs are stored -- no reference source.
 
-usage: python tests/golden/make_golden.py [--seeds 0-11]
+usage: python tests/golden/make_golden.py [--seeds 0-11] [--msa-only]
 """
 import argparse
 import gzip
@@ -51,10 +52,11 @@ def sha(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", default="0-11")
+    ap.add_argument("--msa-only", action="store_true", help="only tests/golden/msa_vectors.json.gz")
     a = ap.parse_args()
     lo, hi = a.seeds.split("-")
     index = {}
-    for seed in range(int(lo), int(hi) + 1):
+    for seed in ([] if a.msa_only else range(int(lo), int(hi) + 1)):
         with tempfile.TemporaryDirectory() as d:
             args = T.make_case(seed, d)
             fa, sam = args[-2], args[-1]
@@ -75,9 +77,16 @@ def main():
                                             contigs=out_fa.count(b">"), graph_lines=out_g.count(b"\n"),
                                             trace_lines=out_tr.count(b"\n"), checked_against_shipped_binary=True)
             print("case%02d" % seed, index["case%02d" % seed]["contigs"], "contigs", flush=True)
-    json.dump(index, open(os.path.join(HERE, "index.json"), "w"), indent=1, sort_keys=True)
+    if not a.msa_only:
+        json.dump(index, open(os.path.join(HERE, "index.json"), "w"), indent=1, sort_keys=True)
 
     # MSA vectors (row a7): sequences in the order the caller passes them (length descending)
+    def msa_ref(seqs):
+        p = subprocess.run([MSA_REF], input=("\n".join(seqs) + "\n").encode(), stdout=subprocess.PIPE)
+        assert p.returncode == 0
+        lines = p.stdout.decode().splitlines()
+        return dict(seqs=seqs, rows=lines[:len(seqs)], ncol=int(lines[len(seqs)].split()[1]))
+
     rng = random.Random(11)
     cases = []
     for it in range(120):
@@ -85,9 +94,10 @@ def main():
         alpha = "ACGT" if it % 4 else "ACGTacgtN-"
         seqs = ["".join(rng.choice(alpha) for _ in range(rng.randint(1, 12))) for _ in range(n)]
         seqs.sort(key=len, reverse=True)
-        p = subprocess.run([MSA_REF], input=("\n".join(seqs) + "\n").encode(), stdout=subprocess.PIPE)
-        lines = p.stdout.decode().splitlines()
-        cases.append(dict(seqs=seqs, rows=lines[:n], ncol=int(lines[n].split()[1])))
+        cases.append(msa_ref(seqs))
+    import graph_edge_lib
+    for name in sorted(graph_edge_lib.MSA_CASES):
+        cases.append(dict(msa_ref(graph_edge_lib.MSA_CASES[name]().seqs), name=name))
     with gzip.GzipFile(os.path.join(HERE, "msa_vectors.json.gz"), "wb", mtime=0) as f:
         f.write(json.dumps(cases).encode())
     print("msa vectors", len(cases))

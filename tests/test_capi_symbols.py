@@ -50,3 +50,18 @@ def test_product_never_touches_oracle():
                 if re.search(r"oracle/|liboracle|straincall_oracle|import\s+oracle", txt):
                     bad.append(os.path.join(dirpath, f))
     assert bad == []
+
+
+def test_graph_stage_test_entries_are_declared_and_bound():
+    """sc_roi_thread_edges and sc_edge_support_tables (test entries): in the header, exported, bound with as many arguments
+    as the header declares; sc_roi_thread_tables keeps its ten."""
+    from rambl_amd import capi
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "straincall_hip.h")).read(), flags=re.S)
+    lib = capi.load_library()
+    for name, n_args in (("sc_roi_thread_edges", 7), ("sc_edge_support_tables", 11), ("sc_roi_thread_tables", 10)):
+        decl = re.search(r"\bint %s\s*\(([^)]*)\)" % name, hdr)
+        assert decl and len(decl.group(1).split(",")) == n_args, name
+        assert name in capi.EXPORTS
+        f = getattr(lib, name)
+        assert len(f.argtypes) == n_args and f.restype is ctypes.c_int, name
+    assert hasattr(capi.Context, "thread_edges") and hasattr(capi.Context, "edge_support_tables")
