@@ -183,8 +183,8 @@ int sc_edge_support_tables(sc_ctx* ctx, int n_nodes, const int* pool_ptr, const 
  * ent_cn, one-symbol label ent_sym < 16, or 0xFF: no single symbol, drawn but not counted) start
  * at entry index e0 (the entries in front name other reads); mates as a CSR over the reads (mate_off[n_reads+1], mate_idx, -1: none); n_sweeps sweeps,
  * draw t taking U[t] (n_u >= n_sweeps * sum ent_cn <= 40000).  Out: kdraw[S] draws per strain,
- * cnt[S*16] draws per (strain, read symbol), out[5] = draws, draws of the fp64 scan tier, draws of
- * the literal tier, window passes, kernel variant.  Only on a context of one stream (SC_ERR_ARG
+ * cnt[S*16] draws per (strain, read symbol), out[6] = draws, draws of the fp64 scan tier, draws of
+ * the literal tier, window passes, kernel variant, the pieces of the level that ran on a grid in front of it (LV_* bits).  Only on a context of one stream (SC_ERR_ARG
  * otherwise: resident level workers run the same level body). */
 int sc_sample_level(sc_ctx* ctx, int S, const double* a0, int n_reads, const double* ll, const unsigned char* has,
                     int n_ent, int e0, const int* ent_rid, const int* ent_cn, const int* ent_sym, const int* mate_off,

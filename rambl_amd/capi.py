@@ -517,7 +517,7 @@ class Context:
     def sample_level(self, a0, ll, has, ent_rid, ent_cn, ent_sym, mates, n_sweeps, U, e0=1):
         """Row a14 on its own (a test entry): one sampler level through the production kernel with the uniforms `U`.
         ll: [S][n_reads] log-likelihoods, has: [n_reads] presence, mates: per read a list of mate ids (-1: none).
-        Returns dict(kdraw[S], cnt[S][16], n_draws, n_slow, n_exact, n_pass, kind)."""
+        Returns dict(kdraw[S], cnt[S][16], n_draws, n_slow, n_exact, n_pass, kind, done: the pieces that ran on a grid)."""
         import numpy as np
         a0 = np.ascontiguousarray(a0, dtype=np.float64)
         ll = np.ascontiguousarray(ll, dtype=np.float64)
@@ -533,7 +533,7 @@ class Context:
         U = np.ascontiguousarray(U, dtype=np.float64)
         kdraw = np.zeros(S, dtype=np.uint32)
         cnt = np.zeros((S, 16), dtype=np.uint32)
-        out = (C.c_long * 5)()
+        out = (C.c_long * 6)()
 
         def ptr(x, t):
             return x.ctypes.data_as(C.POINTER(t))
@@ -543,7 +543,7 @@ class Context:
                                       ptr(kdraw, C.c_uint), ptr(cnt, C.c_uint), out)
         if rc != SC_OK:
             raise self._err(rc)
-        return dict(kdraw=kdraw, cnt=cnt, n_draws=out[0], n_slow=out[1], n_exact=out[2], n_pass=out[3], kind=out[4])
+        return dict(kdraw=kdraw, cnt=cnt, n_draws=out[0], n_slow=out[1], n_exact=out[2], n_pass=out[3], kind=out[4], done=out[5])
 
     def msa_align(self, seqs):
         """Row a7: rows of the progressive sum-of-pairs MSA of `seqs` (in the given order)."""

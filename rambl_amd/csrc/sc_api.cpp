@@ -329,7 +329,7 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         DevBuf b_u, b_uf;
         jd.U = upload(w.passthrough, b_u, u, st);
         jd.Uf = upload(w.passthrough, b_uf, uf, st);
-        const JobDev* jd_dev = (const JobDev*)w.b_jobdev.ensure(sizeof(JobDev));
+        const JobDev* jd_dev = (const JobDev*)w.b_jobdev.ensure(sizeof(JobBlock));
         HIPCHK(hipMemcpyAsync((void*)jd_dev, &jd, sizeof jd, hipMemcpyHostToDevice, st));
 
         LevelParams& P = *w.Ph;
@@ -338,17 +338,16 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         H.mode = MODE_SAMPLE; H.S = S; H.e0 = e0; H.e1 = E; H.Q = (int)Q; H.n_sweeps = n_sweeps;
         H.n_copy = 0; H.do_update = 0; H.seq = 1;
         std::memset(w.Rh, 0, sizeof(LevelResult));
-        LevelBatch batch;
-        batch.it[0] = w.level_item(jd_dev, H, KMAX);
-        const int kind = item_kind(batch.it[0].kind);
-        launch_level_batch(st, kind, batch, 1);
+        const LevelItem it = w.level_item(jd_dev, H, KMAX);
+        const int kind = item_kind(it.kind);
+        const int done = launch_level(st, it, n_reads);      // as the walk of a single region launches its levels
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
         const LevelResult& R = *w.Rh;
         if (R.seq != 1u || R.error) throw ScError(SC_ERR_INTERNAL, "the sampler level did not complete");
         for (int s = 0; s < S; s++) kdraw[s] = R.kdraw[s];
         std::memcpy(cnt, R.cnt, sizeof(unsigned) * (size_t)S * KMAX);
-        out[0] = (long)R.n_draws; out[1] = (long)R.n_slow; out[2] = (long)R.n_exact; out[3] = (long)R.n_pass; out[4] = kind;
+        out[0] = (long)R.n_draws; out[1] = (long)R.n_slow; out[2] = (long)R.n_exact; out[3] = (long)R.n_pass; out[4] = kind; out[5] = done;
         return SC_OK;
     } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
     catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }

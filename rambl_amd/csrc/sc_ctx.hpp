@@ -31,8 +31,9 @@ void launch_msa(hipStream_t st, const MsaDev& d);
 void launch_thread(hipStream_t st, const ThreadDev& d, int* pool_sorted);
 int init_graph_kernels();
 // ... and in sc_level.hip
-bool level_wants_grid(const JobDev& job, const LevelHdr& h);
-int launch_level_grid(hipStream_t st, const JobDev& job, const LevelHdr& h, const LevelParams* Pd, LevelResult* R);
+bool level_wants_grid(int n_reads, const LevelHdr& h);
+int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const LevelParams* P, LevelResult* R, bool lone);
+int launch_level(hipStream_t st, const LevelItem& it, int n_reads);
 int level_kind(const LevelHdr& h);
 int level_lds_kb(const LevelHdr& h, int K);
 int level_table_capacity();
@@ -226,12 +227,13 @@ struct Worker {
     std::atomic<double> t_posted{0};  // when the level was handed over (the heart thread judges resident workgroups by it)
     double t_batch_launched = 0;      // diagnostics: when the level's batch was launched, and its size
     int batch_n = 0;
+    int level_done = 0;               // diagnostics: the LV_* pieces of the last level that ran on a grid
     hipEvent_t ev0 = nullptr, ev1 = nullptr;     // the pair of the level being launched (from ev_pool when timing)
     std::vector<hipEvent_t> ev_pool;  // want_timing: one pair per sampler level of the region, read when the region is done
     size_t ev_used = 0;
     LevelParams* Ph = nullptr;        // host-mapped: written here, read by the level's kernel over PCIe
     LevelParams* Pm = nullptr;        //   its device address
-    LevelParams* Pd = nullptr;        // device copy, only for the grid kernels of very large levels
+    LevelParams* Pd = nullptr;        // device copy, only for the grid kernels of very large levels in a context of several regions
     LevelResult* Rh = nullptr;        // host-mapped, written by the kernel, stamped last
     LevelResult* Rd = nullptr;
     bool own_blocks = false;          // Ph / Pd / Rh are this worker's own allocations (a private worker: init_private)
@@ -254,7 +256,7 @@ struct Worker {
     void init_private(Ctx* c);
     void run();
     void process(Job& job);
-    void complete_level(const LevelItem& it, bool timed);
+    void complete_level(const LevelItem& it, int n_reads, bool timed);
     void wait_level();
     void finish_level(int state, const char* err = nullptr);
     void sync_stream();

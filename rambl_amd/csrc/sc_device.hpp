@@ -50,6 +50,14 @@ struct JobDev {
     long dlog_cap;               // the largest n_sweeps * Q of the region's levels
 };
 
+// The region's block in device memory: its JobDev, written once per region, and behind it the 100 MHz tick at which the
+// first kernel of the current level began, when that is a grid kernel in front of the level's own on the same stream
+// (LV_TICKED in LevelHdr::done).
+struct JobBlock {
+    JobDev job;
+    unsigned long long t0;
+};
+
 // Per-level parameters.  The scalars travel as kernel arguments (LevelHdr); the per-strain part lives
 // in host-mapped pinned memory that the kernel of the level reads directly over PCIe, once, into LDS
 // (no copy in front of the launch).  Only the first h.S entries of `sp` / rows of `lpt` and the first
@@ -64,7 +72,7 @@ struct LevelHdr {
     int n_sweeps;                // min(5000, 40000/Q)
     int n_copy;                  // row copies to perform first
     int do_update;               // apply the level's read log-likelihood update (not for read_assign)
-    int done;                    // LV_* pieces already run by grid kernels (very large levels only)
+    int done;                    // LV_* pieces already run by grid kernels in front of the level's own
     int copy_n;                  // leading cells of a row that can hold a value yet (reads and mates met so far): what a row copy moves
     unsigned seq;                // completion stamp the kernel stores into LevelResult::seq when it is done
 };
@@ -113,7 +121,7 @@ __host__ __device__ __forceinline__ void with_sampler_variant(int kind, F&& f) {
 // result blocks.  MAXB keeps the segment below 4 KB.
 struct LevelResult;
 struct LevelItem {
-    const JobDev* job;           // device memory; constant while the region is walked
+    const JobDev* job;           // device memory (the JobDev of a JobBlock); constant while the region is walked
     LevelHdr h;
     int kind;                    // pack_kind(level_kind(h), level_lds_kb(h, K)): the variant of the level kernel that serves it, its LDS need
     const LevelParams* P;        // host-mapped
@@ -162,7 +170,7 @@ struct LevelResult {
     unsigned long long n_pass;   // window passes of the sampler chain
     unsigned long long chain_cycles, chain_wall;   // shader cycles / 100 MHz ticks spent in the urn chain
     unsigned long long n_exact;  // draws resolved by the literal fp64 path
-    unsigned long long level_wall;                 // 100 MHz ticks from the start of the level's kernel to its end
+    unsigned long long level_wall;                 // 100 MHz ticks the GPU spent on the level: from the start of its kernel, or of the first grid kernel in front of it on the same stream (LV_TICKED)
     unsigned phase_ticks[6];     // diagnostics: 100 MHz ticks at the end of staging / copies / update / slots / table / chain
     int error;
     int xcc;                     // XCD the level's workgroup ran on (HW_REG_XCC_ID)

@@ -7,7 +7,8 @@
 //   k_level          one level without the sampler: the update (a13) and the soft
 //                    update (a15, hard_clustering)
 //   k_level_any / k_level_resident   a batch of levels of any kind / the resident level workers
-//   k_level_copy/update/has, k_hard_*   the pieces of a very large level on a grid
+//   k_level_copy/update/entries/rows, k_hard_*   the pieces of a level on a grid, in front of its workgroup: of a very
+//                    large level, or of any level of a context that walks a single region (launch_level)
 //
 // These are integer / fp32 / fp64 loops bound by latency or HBM: no MFMA.
 #include <hip/hip_runtime.h>
@@ -31,9 +32,10 @@ static_assert(LDS_BIG >= (int)(sizeof(double) * MAXS * 64), "LDS_BIG");    // ev
 // --------------------------------------------------------------------------
 // The pieces of one level of the walk (NonparametricClustering.cpp:284-458) that every mode shares.  They
 // run inside the level's single workgroup (k_level_sample / k_level); for levels with hundreds of thousands
-// of (strain, read) items the host runs the first two on a grid instead (k_level_copy, k_level_update) and
-// says so in LevelHdr::done.
-enum { LV_COPIES_DONE = 1, LV_ITEMS_DONE = 2, LV_HAS_DONE = 4, LV_HARD_DONE = 8 };
+// of (strain, read) items, or in a context whose only region leaves the other CUs idle, the host runs them on a grid
+// in front (k_level_copy, k_level_update, k_level_entries, k_level_rows) and says so in LevelHdr::done.
+// LV_TICKED: the first of them has left its tick in JobBlock::t0 (the level's kernel follows on the same stream).
+enum { LV_COPIES_DONE = 1, LV_ITEMS_DONE = 2, LV_HAS_DONE = 4, LV_HARD_DONE = 8, LV_SLOTS_DONE = 16, LV_ROWS_DONE = 32, LV_TICKED = 64 };
 // The region's arrays as the batched level kernels see them: a block of device memory that does not change while the
 // region is walked, read through the constant address space -- scalar loads the compiler may repeat at will, exactly
 // like kernel arguments (which hold only a pointer to it: LevelItem).
@@ -74,7 +76,7 @@ __device__ __forceinline__ void phase_copies(const JD& job, const LevelHdr& h, c
 }
 
 // The loops below that the grid kernels share take a first index and a step: tid, nt inside the level's workgroup, the
-// global index and the size of the grid in k_level_has / k_hard_*.
+// global index and the size of the grid in k_level_entries / k_level_rows / k_hard_*.
 
 // the level's reads are present in read_loglik from here on
 template <class JD>
@@ -187,7 +189,7 @@ __device__ __forceinline__ void phase_update(const JD& job, const LevelHdr& h, c
     } else {
         if (tid < S) for (int r = 0; r < Rn; r++) item(tid, r);
     }
-    if (h.done & LV_HAS_DONE) { __syncthreads(); return; }      // (k_level_has, behind the grid's update; the barrier is the phase's)
+    if (h.done & LV_HAS_DONE) { __syncthreads(); return; }      // (k_level_entries, behind the grid's update; the barrier is the phase's)
     __syncthreads();
     mark_present(job, h, tid, nt);
     __syncthreads();
@@ -229,15 +231,15 @@ __device__ __forceinline__ void finish_level(const LevelHdr& h, LevelResult* __r
 // The pieces of hard_clustering (NonparametricClustering.cpp:17-125) that the level's workgroup (level_plain_body) and
 // the grid (k_hard_*) both run.
 
-// logprob(uid) inserts a zero log-likelihood for a mate not seen yet (Strain.cpp:147-150).  sp: the strains' parameters,
-// in LDS or in device memory.
-template <class JD>
-__device__ __forceinline__ void zero_unseen_mates(const JD& job, const LevelHdr& h, const StrainParam* sp, int first, int step) {
+// logprob(uid) inserts a zero log-likelihood for a mate not seen yet (Strain.cpp:147-150).  slot_of(s): the strain's row,
+// out of LDS.
+template <class JD, class SL>
+__device__ __forceinline__ void zero_unseen_mates(const JD& job, const LevelHdr& h, SL slot_of, int first, int step) {
     const long stride = job.ll_stride;
     for (int q = first; q < h.Q; q += step) {
         const int uid = job.quid[q];
         if (uid >= 0 && !job.has[uid])
-            for (int s = 0; s < h.S; s++) job.ll[(long)sp[s].slot * stride + uid] = 0.0;
+            for (int s = 0; s < h.S; s++) job.ll[(long)slot_of(s) * stride + uid] = 0.0;
     }
 }
 
@@ -272,6 +274,73 @@ __device__ __forceinline__ void strain_sums(const double* prow, const uint8_t* q
         double v = acc[b];
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
         acc[b] = v;
+    }
+}
+
+// phase 3: what the sampler draws from.  Per draw slot q the fp32 weight row L[q][s] = exp(x_s - max_s x_s),
+// x_s = ll(read) + ll(mate) in fp64, zeros behind it up to the stride, and 16 zeros behind the last row.  A slot whose
+// log-likelihoods lie in the underflow range of the reference's exp() gets a NaN row, which sends its draws to the
+// checked tiers.  put4(index, four floats) stores them: into LDS or tabLf inside the workgroup, into tabLf on the grid
+// (k_level_rows).  s_slot: the strains' rows, in LDS.
+//
+// A lane takes a draw slot q and walks the strains: the 64 slots of a wavefront are neighbouring reads (slots follow
+// the level's entries, entries the read ids), so one load instruction -- one strain's row at 64 nearby read ids --
+// touches a dozen cache lines instead of 64.  (A lane used to take eight strains of one slot: every 8-byte cell came
+// with its own 128-byte line from the L2, 3.3 MB per level of 860 read copies x 30 strains at the 64 bytes a clock a
+// compute unit gets -- 25 us, the longest part of a level outside the chain.)  Up to 32 strains the cells stay in
+// registers between the maximum and the exponentials; beyond, they are read a second time (from the L1 / L2).
+template <int NB, class JD, class PUT>
+__device__ __forceinline__ void weight_rows(const JD& job, const LevelHdr& h, const int* s_slot, PUT put4, int first, int step) {
+    constexpr int SR = (NB <= 2) ? 16 * NB : 16;           // cells held per lane
+    const int S = h.S, Q = h.Q, e0 = h.e0;
+    const int stride = chain_w_stride(S);
+    const long lstride = job.ll_stride;
+    const float qnanf = __int_as_float(0x7fc00000);
+    for (int q = first; q < Q; q += step) {
+        const int rid = job.ent_rid[e0 + job.qent[q]], uid = job.quid[q];
+        const bool hr = h.do_update ? true : job.has[rid] != 0;      // the update has just entered the level's reads
+        const bool hu = uid >= 0 && job.has[uid] != 0;
+        const long Lf = (long)q * stride;
+        auto cell = [&](int sx) __attribute__((always_inline)) -> double {
+            const double* row = job.ll + (long)s_slot[sx] * lstride;
+            double v = hr ? row[rid] : 0.0;
+            if (hu) v += row[uid];
+            return v;
+        };
+        double m = -INFINITY;
+        double x[SR];
+        if (NB <= 2) {
+#pragma unroll
+            for (int i = 0; i < SR; i++) { x[i] = -INFINITY; if (i < S) { x[i] = cell(i); m = fmax(m, x[i]); } }
+        } else {
+            for (int s0 = 0; s0 < S; s0 += SR) {
+#pragma unroll
+                for (int i = 0; i < SR; i++) if (s0 + i < S) m = fmax(m, cell(s0 + i));
+            }
+        }
+        const bool flag = !(m >= -600.0);                // underflow range of the reference's exp(); also NaN / -inf
+        // the row: S weights, the symbol, zeros up to the stride (a multiple of four floats)
+        for (int s0 = 0; s0 < stride; s0 += SR) {
+            if (NB > 2) {
+#pragma unroll
+                for (int i = 0; i < SR; i++) x[i] = (s0 + i < S) ? cell(s0 + i) : -INFINITY;
+            }
+#pragma unroll
+            for (int i = 0; i < SR; i += 4) {
+                if (s0 + i < stride) {
+                    f4v w;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int sx = s0 + i + k;
+                        const float wk = sx < S ? (flag ? qnanf : exp_weight(x[i + k] - m)) : 0.0f;
+                        if (k == 0) w.x = wk; else if (k == 1) w.y = wk; else if (k == 2) w.z = wk; else w.w = wk;
+                    }
+                    put4(Lf + s0 + i, w);
+                }
+            }
+        }
+        // the chain reads whole 16-strain blocks: keep what follows the last row finite
+        if (q == Q - 1) for (int i = 0; i < 16; i += 4) put4(Lf + stride + i, f4v{0.0f, 0.0f, 0.0f, 0.0f});
     }
 }
 
@@ -321,6 +390,13 @@ __device__ __forceinline__ LevelHdr load_hdr(const IT& it) {
 }
 // What both bodies begin with: the level's scalars out of the item, the per-strain parameters into LDS (the log tables
 // into the big region where the body's own update will read them), the result block reset, the first tick.
+// The level began with its first kernel: a grid kernel in front on the same stream has left its tick behind the region's
+// JobDev.  (Not so for the grid kernels of a context with several regions: a host round trip and the hand-over to the
+// level server or a resident worker lie between them and this kernel, which is no time the GPU spent on the level.)
+template <class IT>
+__device__ __forceinline__ unsigned long long level_wall0(const IT& it) {
+    return (it.h.done & LV_TICKED) ? reinterpret_cast<const JobBlock*>(it.job)->t0 : wall_clock64();
+}
 template <class IT>
 __device__ __forceinline__ LevelHdr begin_level(const IT& it, const LevelLds& l, unsigned long long wall0, int tid, int nt) {
     const LevelHdr h = load_hdr(it);
@@ -335,7 +411,7 @@ __device__ __forceinline__ LevelHdr begin_level(const IT& it, const LevelLds& l,
 }
 template <int NB, bool ROWS_LDS, bool STAY, class IT>
 __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s_raw) {
-    const unsigned long long wall0 = wall_clock64();
+    const unsigned long long wall0 = level_wall0(it);
     KJob& job = *(KJob*)it.job;
     LevelResult* __restrict__ R = it.R;
     const LevelLds l = level_lds(s_raw);
@@ -344,7 +420,7 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
     const int tid = threadIdx.x;
     int nt = blockDim.x;
     const LevelHdr h = begin_level(it, l, wall0, tid, nt);
-    const int S = h.S, Q = h.Q, e0 = h.e0, Rn = h.e1 - h.e0;
+    const int S = h.S, Q = h.Q, Rn = h.e1 - h.e0;
     const int stride = chain_w_stride(S);
     const bool upd = h.do_update && Rn > 0;
     for (int i = tid; i < MAXS * KMAX; i += nt) l.s_cnt[i] = 0;
@@ -358,78 +434,26 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
     if (tid == 0) R->phase_ticks[1] = (unsigned)(wall_clock64() - wall0);
     // the draw slots depend on the level's entries alone: their loads and stores go out in front of the update's, and
     // the update's closing barriers cover them (phase_ticks[3] - [2] is therefore ~0 on a level with an update)
+    const bool slots = !(h.done & LV_SLOTS_DONE);            // (else k_level_entries has written them)
     if (upd) {
-        phase_slots<false>(job, h, tid, nt);
+        if (slots) phase_slots<false>(job, h, tid, nt);
         phase_update(job, h, l.s_sp, l.s_lab, reinterpret_cast<const double*>(l.s_big), tid, nt);
     }
     if (tid == 0) R->phase_ticks[2] = (unsigned)(wall_clock64() - wall0);
-    if (!upd) phase_slots(job, h, tid, nt);
+    if (!upd && slots) phase_slots(job, h, tid, nt);
     if (tid == 0) R->phase_ticks[3] = (unsigned)(wall_clock64() - wall0);
 
-    // what the sampler draws from.  Per draw slot q the fp32 weight row L[q][s] = exp(x_s - max_s x_s),
-    // x_s = ll(read) + ll(mate) in fp64, zeros behind it up to the stride.  G lanes share a slot, each walks
-    // <= 8 strains; the max is joined by shuffles.  A slot whose log-likelihoods lie in the underflow range of
-    // the reference's exp() gets a NaN row, which sends its draws to the checked tiers.
-    {
-        // A lane takes a draw slot q and walks the strains: the 64 slots of a wavefront are neighbouring reads (slots follow
-        // the level's entries, entries the read ids), so one load instruction -- one strain's row at 64 nearby read ids --
-        // touches a dozen cache lines instead of 64.  (A lane used to take eight strains of one slot: every 8-byte cell came
-        // with its own 128-byte line from the L2, 3.3 MB per level of 860 read copies x 30 strains at the 64 bytes a clock a
-        // compute unit gets -- 25 us, the longest part of a level outside the chain.)  Up to 32 strains the cells stay in
-        // registers between the maximum and the exponentials; beyond, they are read a second time (from the L1 / L2).
-        constexpr int SR = (NB <= 2) ? 16 * NB : 16;           // cells held per lane
-        const long lstride = job.ll_stride;
+    if (!(h.done & LV_ROWS_DONE)) {
         SC_GLOBAL float* rows_g = (SC_GLOBAL float*)job.tabLf;
-        auto put4 = [&](long idx, f4v v) __attribute__((always_inline)) {
+        weight_rows<NB>(job, h, l.s_slot, [&](long idx, f4v v) __attribute__((always_inline)) {
             if (ROWS_LDS) *(f4v*)(s_rows + idx) = v; else *(SC_GLOBAL f4v*)(rows_g + idx) = v;
-        };
-        const float qnanf = __int_as_float(0x7fc00000);
-        for (int q = tid; q < Q; q += nt) {
-            const int rid = job.ent_rid[e0 + job.qent[q]], uid = job.quid[q];
-            const bool hr = h.do_update ? true : job.has[rid] != 0;      // the update has just entered the level's reads
-            const bool hu = uid >= 0 && job.has[uid] != 0;
-            const long Lf = (long)q * stride;
-            auto cell = [&](int sx) __attribute__((always_inline)) -> double {
-                const double* row = job.ll + (long)l.s_slot[sx] * lstride;
-                double v = hr ? row[rid] : 0.0;
-                if (hu) v += row[uid];
-                return v;
-            };
-            double m = -INFINITY;
-            double x[SR];
-            if (NB <= 2) {
-#pragma unroll
-                for (int i = 0; i < SR; i++) { x[i] = -INFINITY; if (i < S) { x[i] = cell(i); m = fmax(m, x[i]); } }
-            } else {
-                for (int s0 = 0; s0 < S; s0 += SR) {
-#pragma unroll
-                    for (int i = 0; i < SR; i++) if (s0 + i < S) m = fmax(m, cell(s0 + i));
-                }
-            }
-            const bool flag = !(m >= -600.0);                // underflow range of the reference's exp(); also NaN / -inf
-            // the row: S weights, the symbol, zeros up to the stride (a multiple of four floats)
-            for (int s0 = 0; s0 < stride; s0 += SR) {
-                if (NB > 2) {
-#pragma unroll
-                    for (int i = 0; i < SR; i++) x[i] = (s0 + i < S) ? cell(s0 + i) : -INFINITY;
-                }
-#pragma unroll
-                for (int i = 0; i < SR; i += 4) {
-                    if (s0 + i < stride) {
-                        f4v w;
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const int sx = s0 + i + k;
-                            const float wk = sx < S ? (flag ? qnanf : exp_weight(x[i + k] - m)) : 0.0f;
-                            if (k == 0) w.x = wk; else if (k == 1) w.y = wk; else if (k == 2) w.z = wk; else w.w = wk;
-                        }
-                        put4(Lf + s0 + i, w);
-                    }
-                }
-            }
-            // the chain reads whole 16-strain blocks: keep what follows the last row finite
-            if (q == Q - 1) for (int i = 0; i < 16; i += 4) put4(Lf + stride + i, f4v{0.0f, 0.0f, 0.0f, 0.0f});
-        }
+        }, tid, nt);
+    } else if (ROWS_LDS) {
+        // k_level_rows has built them in tabLf: Q rows and the 16 zeros behind the last, 16 bytes a load
+        const f4v* src = reinterpret_cast<const f4v*>(job.tabLf);
+        f4v* dst = reinterpret_cast<f4v*>(s_rows);
+        const int n4 = (Q * stride + 16) >> 2;
+        for (int i = tid; i < n4; i += nt) dst[i] = src[i];
     }
     __syncthreads();
     if (tid == 0) R->phase_ticks[4] = (unsigned)(wall_clock64() - wall0);
@@ -452,7 +476,7 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
 // the soft update hard_clustering (NonparametricClustering.cpp:17-125).  Single workgroup.
 template <class IT>
 __device__ __forceinline__ void level_plain_body(const IT& it, unsigned char* s_raw) {
-    const unsigned long long wall0 = wall_clock64();
+    const unsigned long long wall0 = level_wall0(it);
     KJob& job = *(KJob*)it.job;
     LevelResult* __restrict__ R = it.R;
     const LevelLds l = level_lds(s_raw);
@@ -473,7 +497,7 @@ __device__ __forceinline__ void level_plain_body(const IT& it, unsigned char* s_
 
     // hard_clustering, NonparametricClustering.cpp:17-125
     const int Q = h.Q;
-    zero_unseen_mates(job, h, l.s_sp, tid, nt);
+    zero_unseen_mates(job, h, [&](int s) { return l.s_sp[s].slot; }, tid, nt);
     __syncthreads();
     for (int q = tid; q < Q; q += nt) { const int uid = job.quid[q]; if (uid >= 0) job.has[uid] = 1; }
     __syncthreads();
@@ -649,35 +673,56 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_level_resident(ResidentArgs a
         __hip_atomic_store(&mb->state, s_cmd == 2 ? 3u : 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
+// --------------------------------------------------------------------------
+// The pieces of a level on a grid.  Each is a kernel of its own, launched in stream order in front of the level's
+// kernel: a kernel boundary is the only synchronisation between them.  They find the region through the pointer to
+// its JobDev, as the level kernels do, and the level's parameters behind P: a device copy (a very large level of a
+// context with several regions, launched from the set-up stream) or the host-mapped block itself (launch_level), of
+// which a workgroup then reads only what its own items need.  The first kernel of a level leaves its tick in JobBlock::t0.
+__device__ __forceinline__ void grid_tick(unsigned long long* t0) {
+    if (t0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *t0 = wall_clock64();
+}
+
 // grid, phase 0: rows of strains created by the last extension (Strain copy, Strain.cpp:73-83); copies are
-// independent (a destination row is a free row, a source row a surviving parent's).  P: device copy.
-__global__ __launch_bounds__(256) void k_level_copy(JobDev job, const LevelParams* __restrict__ P) {
+// independent (a destination row is a free row, a source row a surviving parent's).  As in phase_copies, cells past
+// copy_n hold nothing yet.
+__global__ __launch_bounds__(256) void k_level_copy(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, unsigned long long* t0) {
+    grid_tick(t0);
+    KJob& job = *(KJob*)jp;
     const int c = blockIdx.y;
     const double2* src = reinterpret_cast<const double2*>(job.ll + (long)P->copy_src[c] * job.ll_stride);
     double2* dst = reinterpret_cast<double2*>(job.ll + (long)P->copy_dst[c] * job.ll_stride);
-    const int n2 = (job.n_reads + 1) >> 1;
+    const int n2 = ((h.copy_n < job.n_reads ? h.copy_n : job.n_reads) + 1) >> 1;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
-// grid, phase 1, single-symbol labels: ll[s][rid] (+)= log P(read symbol | strain symbol), NonparametricClustering.cpp:343-391
-__global__ __launch_bounds__(256) void k_level_update(JobDev job, LevelHdr h, const LevelParams* __restrict__ P) {
+// grid, phase 1, single-symbol labels: ll[s][rid] (+)= log P(read symbol | strain symbol), NonparametricClustering.cpp:343-391.
+// Item idx is (strain idx / Rn, entry idx % Rn); a workgroup takes a run of consecutive items and stages the slots,
+// labels and table rows of the strains of that run alone.
+__global__ __launch_bounds__(256) void k_level_update(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, unsigned long long* t0) {
     __shared__ double s_row[MAXS * KMAX];       // lpt[s][label of s][b]
     __shared__ double s_diag[MAXS * KMAX];      // lpt[s][b][b]  (an N in the strain label matches the read symbol)
     __shared__ int s_slot[MAXS], s_lab[MAXS];
-    const int tid = threadIdx.x;
+    grid_tick(t0);
+    KJob& job = *(KJob*)jp;
+    const int tid = threadIdx.x, nt = blockDim.x;
     const int S = h.S, K = job.K, e0 = h.e0, Rn = h.e1 - h.e0, codeN = job.code_N;
-    for (int s = tid; s < S; s += blockDim.x) { s_slot[s] = P->sp[s].slot; s_lab[s] = job.labels[P->sp[s].lab_off]; }
+    const long total = (long)S * Rn;
+    const long per = ((total + gridDim.x - 1) / gridDim.x + nt - 1) / nt * nt;
+    const long lo = (long)blockIdx.x * per, hi = lo + per < total ? lo + per : total;
+    if (lo >= hi) return;                                   // (the whole workgroup)
+    const int sa = (int)(lo / Rn), sb = (int)((hi - 1) / Rn);
+    for (int s = sa + tid; s <= sb; s += nt) { s_slot[s] = P->sp[s].slot; s_lab[s] = job.labels[P->sp[s].lab_off]; }
     __syncthreads();
-    for (int i = tid; i < S * KMAX; i += blockDim.x) {
+    for (int i = sa * KMAX + tid; i < (sb + 1) * KMAX; i += nt) {
         const int sx = i / KMAX, b = i % KMAX, a = s_lab[sx];
         const double* lp = P->lpt + (long)sx * K * K;                  // compact [K][K] table of the strain
         s_row[i] = (a < K && b < K) ? lp[a * K + b] : 0.0;
         s_diag[i] = (b < K) ? lp[b * K + b] : 0.0;
     }
     __syncthreads();
-    const long total = (long)S * Rn;
     const long stride = job.ll_stride;
-    for (long idx = (long)blockIdx.x * blockDim.x + tid; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    for (long idx = lo + tid; idx < hi; idx += nt) {
         const int sx = (int)(idx / Rn), e = e0 + (int)(idx % Rn);
         const int rid = job.ent_rid[e];
         const int b = job.labels[job.ent_lab_off[e]];
@@ -692,28 +737,49 @@ __global__ __launch_bounds__(256) void k_level_update(JobDev job, LevelHdr h, co
     }
 }
 
-// grid, after phase 1: the level's reads are present in read_loglik from here on (what the level's own workgroup does with
-// 512 threads -- 117 rounds of two dependent loads on a level of 60 000 entries)
-__global__ __launch_bounds__(256) void k_level_has(JobDev job, LevelHdr h) {
-    mark_present(job, h, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+// grid, per entry of the level.  Behind phase 1 the level's reads are present in read_loglik from here on (what the
+// level's own workgroup does with 512 threads -- 117 rounds of two dependent loads on a level of 60 000 entries); the
+// entry's draw slots (phase_slots), for the sampler's weight rows or the hard update.  Either or both.
+__global__ __launch_bounds__(256) void k_level_entries(const JobDev* jp, LevelHdr h, int has, int slots, unsigned long long* t0) {
+    grid_tick(t0);
+    KJob& job = *(KJob*)jp;
+    const int first = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+    if (has) mark_present(job, h, first, step);
+    if (slots) phase_slots<false>(job, h, first, step);
+}
+
+// grid, phase 3: the sampler's weight rows (weight_rows) into tabLf, whichever variant of the level's kernel follows: one
+// that keeps its rows in LDS copies them from there.  A wavefront per workgroup, a draw slot per lane.
+template <int NB>
+__global__ __launch_bounds__(64) void k_level_rows(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, unsigned long long* t0) {
+    __shared__ int s_slot[MAXS];
+    grid_tick(t0);
+    KJob& job = *(KJob*)jp;
+    for (int s = threadIdx.x; s < h.S; s += blockDim.x) s_slot[s] = P->sp[s].slot;
+    __syncthreads();
+    SC_GLOBAL float* rows_g = (SC_GLOBAL float*)job.tabLf;
+    weight_rows<NB>(job, h, s_slot, [&](long idx, f4v v) __attribute__((always_inline)) { *(SC_GLOBAL f4v*)(rows_g + idx) = v; },
+                    blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // hard_clustering (NonparametricClustering.cpp:17-125) of a level with millions of (strain, draw slot) pairs on a grid --
 // the unthinned configs[3] region has 103 such levels of 26 strains x 110 000 slots, 9-13 ms each inside ONE workgroup.
-// The pieces are the functions level_plain_body runs, called with the grid's index and size: the draw slots (phase_slots);
-// a zero log-likelihood for a mate not seen yet (zero_unseen_mates); per slot the responsibilities (normalise_column; each
-// side fills x and finds its maximum its own way: the workgroup spreads (strain, slot) pairs over its threads, a thread of
-// the grid walks its slot's strains); per strain ONE wavefront that adds its responsibilities (strain_sums): bit-identical
-// results, 100 CUs instead of one.
-__global__ __launch_bounds__(256) void k_hard_slots(JobDev job, LevelHdr h) {
-    phase_slots<false>(job, h, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+// The pieces are the functions level_plain_body runs, called with the grid's index and size: the draw slots (phase_slots,
+// k_level_entries); a zero log-likelihood for a mate not seen yet (zero_unseen_mates); per slot the responsibilities
+// (normalise_column; each side fills x and finds its maximum its own way: the workgroup spreads (strain, slot) pairs over
+// its threads, a thread of the grid walks its slot's strains); per strain ONE wavefront that adds its responsibilities
+// (strain_sums): bit-identical results, 100 CUs instead of one.
+__global__ __launch_bounds__(256) void k_hard_mates(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P) {
+    __shared__ int s_slot[MAXS];
+    KJob& job = *(KJob*)jp;
+    for (int s = threadIdx.x; s < h.S; s += blockDim.x) s_slot[s] = P->sp[s].slot;
+    __syncthreads();
+    zero_unseen_mates(job, h, [&](int s) { return s_slot[s]; }, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
-__global__ __launch_bounds__(256) void k_hard_mates(JobDev job, LevelHdr h, const LevelParams* __restrict__ P) {
-    zero_unseen_mates(job, h, P->sp, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-}
-__global__ __launch_bounds__(256) void k_hard_resp(JobDev job, LevelHdr h, const LevelParams* __restrict__ P) {
+__global__ __launch_bounds__(256) void k_hard_resp(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P) {
     __shared__ int s_slot[MAXS];
     __shared__ double s_logpri[MAXS];
+    KJob& job = *(KJob*)jp;
     const int S = h.S, e0 = h.e0;
     for (int s = threadIdx.x; s < S; s += blockDim.x) { s_slot[s] = P->sp[s].slot; s_logpri[s] = P->sp[s].logpri; }
     __syncthreads();
@@ -734,7 +800,8 @@ __global__ __launch_bounds__(256) void k_hard_resp(JobDev job, LevelHdr h, const
     }
 }
 // one wavefront per strain (= per workgroup of 64)
-__global__ __launch_bounds__(64) void k_hard_sums(JobDev job, LevelHdr h, const LevelParams* __restrict__ P, LevelResult* __restrict__ R) {
+__global__ __launch_bounds__(64) void k_hard_sums(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, LevelResult* __restrict__ R) {
+    KJob& job = *(KJob*)jp;
     const int s = blockIdx.x, lane = threadIdx.x, K = job.K, K2 = K * K, Q = h.Q;
     double acc[KMAX + 1];
     strain_sums(job.tabA + (long)s * job.qcap, job.qcode, Q, lane, acc);
@@ -766,63 +833,89 @@ int init_level_kernels() {
 }
 // doubles of LDS a level can spend on the strains' log tables / the soft update's histogram: S * K * K must fit
 int level_table_capacity() { return LDS_BIG / (int)sizeof(double); }
-// A level of ordinary size is ONE launch (launch_level_batch).  Only when a level has so many (strain, read) items or
-// such long rows that a single workgroup would crawl (unthinned deep coverage) do the row copies and the
-// single-symbol update run on a grid first; `Pd` is then a device copy of the parameters the caller has put
-// in front of these launches on the same stream.  Returns the LV_* bits to pass on in LevelHdr::done.
+// A level of ordinary size is ONE launch (launch_level_batch).  When a level has so many (strain, read) items or such
+// long rows that a single workgroup would crawl (unthinned deep coverage), its row copies, single-symbol update and hard
+// update run on a grid first, in any context.  In a context that walks a single region every other CU is idle anyway:
+// there a level above `wide_min` items runs its copies, update, `has` marks, draw slots and weight rows on a grid.
+// launch_level_grid returns the LV_* bits to pass on in LevelHdr::done.
 constexpr long GRID_ITEMS = 1L << 17;          // (strain, read) items of a level
 constexpr long GRID_COPY_WORDS = 1L << 19;     // doubles copied for new strains
 constexpr long GRID_HARD = 1L << 18;           // (strain, draw slot) pairs of a hard update
+constexpr long WIDE_ITEMS = 1L << 12;          // (strain, read) items of a level of a lone region (profiles/wide_level)
 // SC_GRID_MIN: tests only, read once; replaces all three (0: every level the grid can take goes there, however small)
 static long grid_min(long dflt) {
     static const long forced = [] { const char* e = getenv("SC_GRID_MIN"); return e ? atol(e) : -1L; }();
     return forced >= 0 ? forced : dflt;
+}
+// SC_WIDE_MIN: tests only, read once; replaces WIDE_ITEMS (0: every level of a lone region that can go wide does)
+static long wide_min() {
+    static const long forced = [] { const char* e = getenv("SC_WIDE_MIN"); return e ? atol(e) : -1L; }();
+    return forced >= 0 ? forced : WIDE_ITEMS;
 }
 static bool hard_on_grid(const LevelHdr& h) {
     // (behind the grid's update only: the pieces of a level keep their order)
     return h.mode == MODE_HARD && h.do_update && (long)h.S * (h.e1 - h.e0) > grid_min(GRID_ITEMS) && !h.has_dups && !h.any_multi &&
            (long)h.S * h.Q > grid_min(GRID_HARD) && h.e1 > h.e0;
 }
-bool level_wants_grid(const JobDev& job, const LevelHdr& h) {
+bool level_wants_grid(int n_reads, const LevelHdr& h) {
     const long items = (long)h.S * (h.e1 - h.e0);
-    return (h.do_update && items > grid_min(GRID_ITEMS) && !h.has_dups && !h.any_multi) || (long)h.n_copy * job.n_reads > grid_min(GRID_COPY_WORDS);
+    return (h.do_update && items > grid_min(GRID_ITEMS) && !h.has_dups && !h.any_multi) || (long)h.n_copy * n_reads > grid_min(GRID_COPY_WORDS);
 }
-int launch_level_grid(hipStream_t st, const JobDev& job, const LevelHdr& h, const LevelParams* Pd, LevelResult* R) {
+static int grid_blocks(long n, int per, int most) {
+    const long g = (n + per - 1) / per;
+    return (int)(g < 1 ? 1 : (g > most ? most : g));
+}
+// The grid kernels of a level on `st`, in the order the level's workgroup keeps; P: the level's parameters as the
+// kernels read them (see above).  `lone`: the level of a context that walks a single region.
+int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const LevelParams* P, LevelResult* R, bool lone) {
     const int S = h.S, Rn = h.e1 - h.e0;
+    const long items = (long)S * Rn;
+    const bool upd = h.do_update && Rn > 0;
+    const bool wide = lone && items > wide_min() && Rn > 0 && S > 0;
+    const bool update_on_grid = upd && !h.has_dups && !h.any_multi && (items > grid_min(GRID_ITEMS) || wide);
+    // the weight rows read what the update writes and the `has` marks behind it: behind the grid's update, or on a level
+    // without one (read_assign)
+    const bool rows_on_grid = wide && kind_has_sampler(kind) && h.Q > 0 && (update_on_grid || !upd);
+    const bool hard = update_on_grid && hard_on_grid(h);
     int done = 0;
-    const bool update_on_grid = h.do_update && (long)S * Rn > grid_min(GRID_ITEMS) && !h.has_dups && !h.any_multi;
+    unsigned long long* t0 = lone ? &reinterpret_cast<JobBlock*>(const_cast<JobDev*>(job))->t0 : nullptr;      // for the level's first kernel
     // The rows of the level's new candidates come first, whoever makes them: a candidate's row must be its parent's row of
     // BEFORE this level's update.  (Until round 3 the update could go to the grid while a few small copies stayed with the
     // level's own kernel, which then copied the parent's already updated row over the child's: the child was scored with its
     // parent's symbol at this level.  Levels of more than 131 072 (candidate, read) items with fewer than 2^19 / reads new
     // candidates -- tests/golden/wide_cap120 found it at 121 candidates x 1 085 reads.)
-    if (h.n_copy > 0 && ((long)h.n_copy * job.n_reads > grid_min(GRID_COPY_WORDS) || update_on_grid)) {
-        const int n2 = (job.n_reads + 1) >> 1;
-        int bx = (n2 + 1023) / 1024;
-        bx = bx < 1 ? 1 : (bx > 256 ? 256 : bx);
-        hipLaunchKernelGGL(k_level_copy, dim3(bx, h.n_copy), dim3(256), 0, st, job, Pd);
+    if (h.n_copy > 0 && ((long)h.n_copy * n_reads > grid_min(GRID_COPY_WORDS) || update_on_grid || rows_on_grid)) {
+        const int n = h.copy_n < n_reads ? h.copy_n : n_reads;
+        hipLaunchKernelGGL(k_level_copy, dim3(grid_blocks((n + 1) >> 1, 1024, 256), h.n_copy), dim3(256), 0, st, job, h, P, t0);
+        t0 = nullptr;
         done |= LV_COPIES_DONE;
     }
-    const long items = (long)S * Rn;
     if (update_on_grid) {
-        int g = (int)((items + 511) / 512);
-        g = g < 1 ? 1 : (g > 1024 ? 1024 : g);
-        hipLaunchKernelGGL(k_level_update, dim3(g), dim3(256), 0, st, job, h, Pd);
-        done |= LV_ITEMS_DONE;
-        int gh = (Rn + 255) / 256;
-        hipLaunchKernelGGL(k_level_has, dim3(gh < 1 ? 1 : (gh > 1024 ? 1024 : gh)), dim3(256), 0, st, job, h);
-        done |= LV_HAS_DONE;
-        if (hard_on_grid(h)) {
-            int gq = (h.Q + 255) / 256;
-            gq = gq < 1 ? 1 : (gq > 2048 ? 2048 : gq);
-            hipLaunchKernelGGL(k_hard_slots, dim3(gh < 1 ? 1 : (gh > 1024 ? 1024 : gh)), dim3(256), 0, st, job, h);
-            hipLaunchKernelGGL(k_hard_mates, dim3(gq), dim3(256), 0, st, job, h, Pd);
-            hipLaunchKernelGGL(k_hard_resp, dim3(gq), dim3(256), 0, st, job, h, Pd);
-            hipLaunchKernelGGL(k_hard_sums, dim3(S), dim3(64), 0, st, job, h, Pd, R);
-            done |= LV_HARD_DONE;
-        }
+        hipLaunchKernelGGL(k_level_update, dim3(grid_blocks(items, 512, 1024)), dim3(256), 0, st, job, h, P, t0);
+        t0 = nullptr;
+        done |= LV_ITEMS_DONE | LV_HAS_DONE;
     }
-    return done;
+    // the `has` marks behind the update, and the draw slots of whoever reads them on a grid
+    const bool slots = rows_on_grid || hard;
+    if (update_on_grid || slots) {
+        hipLaunchKernelGGL(k_level_entries, dim3(grid_blocks(Rn, 256, 1024)), dim3(256), 0, st, job, h, update_on_grid ? 1 : 0, slots ? 1 : 0, t0);
+        t0 = nullptr;
+        if (slots) done |= LV_SLOTS_DONE;
+    }
+    if (rows_on_grid) {
+        with_sampler_variant(kind, [&](auto nb, auto) {
+            hipLaunchKernelGGL((k_level_rows<decltype(nb)::value>), dim3(grid_blocks(h.Q, 64, 128)), dim3(64), 0, st, job, h, P, t0);
+        });
+        done |= LV_ROWS_DONE;
+    }
+    if (hard) {
+        const int gq = grid_blocks(h.Q, 256, 2048);
+        hipLaunchKernelGGL(k_hard_mates, dim3(gq), dim3(256), 0, st, job, h, P);
+        hipLaunchKernelGGL(k_hard_resp, dim3(gq), dim3(256), 0, st, job, h, P);
+        hipLaunchKernelGGL(k_hard_sums, dim3(S), dim3(64), 0, st, job, h, P, R);
+        done |= LV_HARD_DONE;
+    }
+    return done ? (done | (lone ? LV_TICKED : 0)) : 0;
 }
 // One launch = the current level of `n` regions whose levels need the same kernel (workgroup b = batch.it[b]).
 // The kind (sc_device.hpp) names that kernel: NB = ceil(S / 16) register blocks, weight rows in LDS where they fit.
@@ -873,6 +966,16 @@ void launch_level_batch(hipStream_t st, int kind, const LevelBatch& b, int n) {
     with_sampler_variant(kind, [&](auto nb, auto rows_lds) {
         hipLaunchKernelGGL((k_level_sample<decltype(nb)::value, decltype(rows_lds)::value>), dim3(n), dim3(CHAIN_THREADS), lds, st, b);
     });
+}
+// One level of a context that launches its own levels (a single region: Worker::complete_level, sc_sample_level): the
+// pieces that go on a grid, then the level's kernel, all on `st` in stream order.  Returns the level's LV_* bits.
+int launch_level(hipStream_t st, const LevelItem& it, int n_reads) {
+    LevelBatch batch;
+    batch.it[0] = it;
+    LevelItem& b = batch.it[0];
+    b.h.done |= launch_level_grid(st, b.job, n_reads, b.h, item_kind(b.kind), b.P, b.R, true);
+    launch_level_batch(st, item_kind(b.kind), batch, 1);
+    return b.h.done;
 }
 // one grid of `slots` resident workgroups, each with the whole LDS of its CU (every variant must fit)
 void launch_resident(hipStream_t st, const ResidentArgs& a, int slots) {

@@ -228,7 +228,7 @@ void Worker::cluster(Job& job, const PoGraph& g, FlatGraph& f) {
     jd.U = ctx->U.d.p;
     jd.Uf = ctx->U.f.p;
     // the batched level kernels find the region through a pointer: the block travels once, with the uploads
-    const JobDev* jd_dev = (const JobDev*)b_jobdev.ensure(sizeof(JobDev));
+    const JobDev* jd_dev = (const JobDev*)b_jobdev.ensure(sizeof(JobBlock));
     stage->h2d((void*)jd_dev, &jd, sizeof jd, st);
 
     // ---- a16: every edge support on the device

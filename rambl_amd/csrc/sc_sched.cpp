@@ -394,8 +394,9 @@ void Worker::finish_level(int state, const char* err) {
 // context posts the level to the region's mailbox, any other launches it: the worker itself when it is the context's
 // only one, the level server otherwise.  The only worker of a context spins for the stamp itself; any other parks until
 // the executors (resident) or the level server have seen it.
-void Worker::complete_level(const LevelItem& it, bool timed) {
+void Worker::complete_level(const LevelItem& it, int n_reads, bool timed) {
     const unsigned want = it.h.seq;
+    level_done = it.h.done;
     const bool alone = ctx->workers.size() == 1;
     if (grid) {
         // the slot's resident workgroup takes the level from its mailbox: the item, then its stamp (release)
@@ -421,13 +422,12 @@ void Worker::complete_level(const LevelItem& it, bool timed) {
         }
         __atomic_store_n(&grid->mail_done[(size_t)m], want, __ATOMIC_RELEASE);
     } else if (alone) {
-        // nobody to batch with: the worker launches its level itself
-        LevelBatch batch;
-        batch.it[0] = it;
+        // nobody to batch with: the worker launches its level itself, with whatever pieces of it go on a grid in front (the
+        // pair of events brackets them all)
         hipStream_t ls = ctx->launch->st;
         if (timed) HIPCHK(hipEventRecord(ev0, ls));
         (void)hipGetLastError();
-        launch_level_batch(ls, item_kind(it.kind), batch, 1);
+        level_done = launch_level(ls, it, n_reads);
         { const hipError_t le = hipGetLastError(); if (le != hipSuccess) throw HipError(std::string("level kernel launch: ") + hipGetErrorString(le)); }
         if (timed) HIPCHK(hipEventRecord(ev1, ls));
         t_batch_launched = now_ms(); batch_n = 1;

@@ -307,11 +307,12 @@ struct LevelWalk {
         const bool chain = (mode == MODE_SAMPLE) && S > 1 && n_sweeps > 0;
         if (mode == MODE_SAMPLE && (long)n_sweeps * Q > jd.dlog_cap) throw ScError(SC_ERR_INTERNAL, "a level draws more than the region's draw log holds");
         const bool timed = chain && pa.want_timing && !w.grid;      // (no launch to bracket with events when the workers are resident)
-        if (level_wants_grid(jd, H)) {
+        const bool lone = !w.grid && w.ctx->workers.size() == 1;      // launches its levels itself, grid kernels included (launch_level)
+        if (!lone && level_wants_grid(jd.n_reads, H)) {
             // a very large level: row copies / the single-symbol update on a grid, from a device copy of the parameters
             const size_t bytes = offsetof(LevelParams, lpt) + sizeof(double) * (size_t)S * K * K;
             HIPCHK(hipMemcpyAsync(w.Pd, w.Ph, bytes, hipMemcpyHostToDevice, w.st));
-            H.done = launch_level_grid(w.st, jd, H, w.Pd, w.Rd);
+            H.done = launch_level_grid(w.st, jd_dev, jd.n_reads, H, level_kind(H), w.Pd, w.Rd, false);
             w.sync_stream();                             // the level's kernel runs on another stream
         }
         const int ms = w.mslot.load(std::memory_order_relaxed);
@@ -329,7 +330,7 @@ struct LevelWalk {
         const double t_launched = level_log ? now_ms() : 0.0;
         lap(0);
         const LevelItem it = w.level_item(jd_dev, H, K);
-        w.complete_level(it, timed);
+        w.complete_level(it, jd.n_reads, timed);
         t_mark = now_ms();                                   // (the wait for the level is not host work)
         sc_stats& stats = job.stats;
         stats.level_launches++;
@@ -343,10 +344,10 @@ struct LevelWalk {
         if (chain) stats.sampler_level_ticks += (long)Rh->level_wall;
         if (level_log) {
             const double t_done = now_ms();
-            fprintf(level_log, "h %d mode %d S %d Q %d n %d level_us %.1f chain_us %.1f cyc %llu passes %llu slow %llu xcc %d ncopy %d multi %d "
+            fprintf(level_log, "h %d mode %d S %d Q %d n %d level_us %.1f chain_us %.1f cyc %llu passes %llu slow %llu xcc %d ncopy %d copyn %d multi %d done %d "
                     "ph %.1f %.1f %.1f %.1f %.1f host_us %.1f wait_us %.1f pend_us %.1f batch %d\n", job.handle, mode, S, Q,
                     n_sweeps, Rh->level_wall * 0.01, chain ? Rh->chain_wall * 0.01 : 0.0, chain ? (unsigned long long)Rh->chain_cycles : 0ull,
-                    chain ? (unsigned long long)Rh->n_pass : 0ull, chain ? (unsigned long long)Rh->n_slow : 0ull, Rh->xcc, H.n_copy, (int)any_multi,
+                    chain ? (unsigned long long)Rh->n_pass : 0ull, chain ? (unsigned long long)Rh->n_slow : 0ull, Rh->xcc, H.n_copy, H.copy_n, (int)any_multi, w.level_done,
                     Rh->phase_ticks[0] * 0.01, Rh->phase_ticks[1] * 0.01, Rh->phase_ticks[2] * 0.01, Rh->phase_ticks[3] * 0.01, Rh->phase_ticks[4] * 0.01,
                     1e3 * (t_launched - t_last_done), 1e3 * (t_done - t_launched), 1e3 * (w.t_batch_launched - t_launched), w.batch_n);
             t_last_done = t_done;
