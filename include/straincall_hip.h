@@ -393,6 +393,38 @@ int sc_profile_counts(int device, const char* gene_text, const long* gene_off, i
                       int n_segs, const int* seg_read, int n_reads, double min_identity_pct, double max_evalue, double ka_lambda,
                       double ka_k, int seeded, long cand_room, int* out_gene, int* out_times, int* out_share, long* out_reads, long cap,
                       long* n_out, sc_profile_count_stats* stats);
+/* A cohort against one resident gene index.  sc_profile_index_create packs the genes (limits and messages
+ * as sc_profile_counts: 1..8192 bases each, checked here) and copies them to `device`, where they stay until
+ * sc_profile_index_free.  The index also keeps, from call to call, the sorted k-mer keys of every seed length a call has
+ * needed so far (k is 11..16: at most six sets, each built by the first call that needs it) and every array a call sets
+ * aside on the device, grown when a call needs more.  One call at a time per index: the calls share those arrays.
+ * sc_profile_index_info: the number of genes, their bases, and the cached seed lengths ascending (cached_k: room for 6);
+ * every out pointer may be null.
+ * sc_profile_index_counts is sc_profile_counts over the reads of several samples at once: read_sample[n_reads] holds the
+ * sample (0..n_samples-1, n_samples in 1..65536) of every read and is non-decreasing -- the samples come one after the
+ * other; a sample may have no read.  Anything else: SC_ERR_ARG.  Out: the distinct rows (sample, gene, times_hit, number of
+ * such genes) in ascending order with the number of reads behind each.  The rows of one sample are exactly the triples
+ * sc_profile_counts returns for that sample's segments alone with the same genes, thresholds and `seeded`: E depends on
+ * the segment's length and the genes' bases only, the order by E6 is an order whatever other lengths the call holds, and
+ * the seed length, taken from all the call's lengths, is a lossless bound for each of them.  Reads of different samples
+ * are different reads; stretches (cand_room) are not cut where a sample ends.  Of the statistics only seed_k may differ
+ * from the per-sample calls'.
+ *   n_index_builds  key sets this call built: 0 when its k was cached or it ran unseeded
+ *   n_allocs        device allocations this call made: 0 when a call that fitted before is repeated */
+typedef struct sc_profile_index sc_profile_index;
+typedef struct sc_profile_cohort_stats {
+    sc_profile_count_stats counts;     /* summed over the call's stretches, as sc_profile_counts fills it */
+    int n_samples;
+    int n_index_builds;
+    long n_allocs;
+} sc_profile_cohort_stats;
+int sc_profile_index_create(int device, const char* gene_text, const long* gene_off, int n_genes, sc_profile_index** index);
+int sc_profile_index_info(const sc_profile_index* index, int* n_genes, long* gene_bases, int* n_cached_k, int* cached_k);
+int sc_profile_index_counts(sc_profile_index* index, const char* seg_text, const long* seg_off, int n_segs, const int* seg_read, int n_reads,
+                            const int* read_sample, int n_samples, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k,
+                            int seeded, long cand_room, int* out_sample, int* out_gene, int* out_times, int* out_share, long* out_reads, long cap,
+                            long* n_out, sc_profile_cohort_stats* stats);
+void sc_profile_index_free(sc_profile_index* index);
 /* E6 of a segment of L bases with doubled raw score score2 against gene_bases gene bases; no device is touched. */
 double sc_profile_evalue6(int L, long gene_bases, int score2, double ka_lambda, double ka_k);
 

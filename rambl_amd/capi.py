@@ -63,6 +63,13 @@ class ScProfileCountStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScProfileCohortStats(C.Structure):
+    _fields_ = ScProfileCountStats._fields_ + [("n_samples", C.c_int), ("n_index_builds", C.c_int), ("n_allocs", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ScTaxaStats(C.Structure):
     _fields_ = [("upload_ms", C.c_double), ("words_ms", C.c_double), ("table_ms", C.c_double), ("score_ms", C.c_double), ("total_ms", C.c_double),
                 ("n_seqs", C.c_long), ("n_words", C.c_long), ("n_genera", C.c_long), ("table_bytes", C.c_long)]
@@ -140,6 +147,12 @@ def load_library():
     lib.sc_profile_seed_length.argtypes = [ip, C.c_int, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, ip]
     lib.sc_profile_counts.argtypes = [C.c_int, cp, lp, C.c_int, cp, lp, C.c_int, ip, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_int, C.c_long, ip, ip, ip, lp, C.c_long, lp, C.POINTER(ScProfileCountStats)]
+    lib.sc_profile_index_create.argtypes = [C.c_int, cp, lp, C.c_int, C.POINTER(vp)]
+    lib.sc_profile_index_info.argtypes = [vp, ip, lp, ip, ip]
+    lib.sc_profile_index_counts.argtypes = [vp, cp, lp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.c_int, C.c_long, ip, ip, ip, ip, lp, C.c_long, lp, C.POINTER(ScProfileCohortStats)]
+    lib.sc_profile_index_free.argtypes = [vp]
+    lib.sc_profile_index_free.restype = None
     lib.sc_profile_evalue6.argtypes = [C.c_int, C.c_long, C.c_int, C.c_double, C.c_double]
     lib.sc_profile_evalue6.restype = C.c_double
     u64, u64p = C.c_ulonglong, C.POINTER(C.c_ulonglong)
@@ -156,7 +169,8 @@ def load_library():
     for f in ("sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads", "sc_profile_hits",
-              "sc_profile_hits_seeded", "sc_profile_seed_length", "sc_profile_counts"):
+              "sc_profile_hits_seeded", "sc_profile_seed_length", "sc_profile_counts", "sc_profile_index_create", "sc_profile_index_info",
+              "sc_profile_index_counts"):
         getattr(lib, f).restype = C.c_int
     for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
               "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level", "sc_roi_thread_edges", "sc_edge_support_tables"):
@@ -169,7 +183,8 @@ EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "
            "sc_roi_thread_tables", "sc_roi_thread_edges", "sc_edge_support_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
            "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
            "sc_align_error", "sc_profile_hits", "sc_profile_error", "sc_profile_hits_seeded", "sc_profile_seed_length",
-           "sc_profile_counts", "sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table", "sc_taxa_free", "sc_taxa_error",
+           "sc_profile_counts", "sc_profile_index_create", "sc_profile_index_info", "sc_profile_index_counts", "sc_profile_index_free",
+           "sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table", "sc_taxa_free", "sc_taxa_error",
            "sc_taxa_draw"]              # (sc_profile_evalue6 as well: load_library looks it up itself; the list holds letter-only names)
 
 
@@ -723,6 +738,98 @@ def profile_counts(genes, segs, seg_read, min_identity=95.0, max_evalue=1e-10, k
             raise StrainCallError(rc, lib().sc_profile_error().decode())
         k = n.value
         return ProfileCounts([(int(gene[i]), int(times[i]), int(share[i]), int(n_behind[i])) for i in range(k)], st)
+
+
+class ProfileCohortCounts:
+    """The result of sc_profile_index_counts: rows = [(sample, gene index, times_hit, number_of_such_genes, reads)] ascending,
+    one entry per distinct row; stats is the ScProfileCohortStats of the call."""
+
+    def __init__(self, rows, stats):
+        self.rows = rows
+        self.stats = stats
+
+    def __len__(self):
+        return len(self.rows)
+
+    def by_sample(self, s):
+        """The (gene index, times_hit, number_of_such_genes, reads) of sample s, as profile.counts_from_triples takes them."""
+        return [r[1:] for r in self.rows if r[0] == s]
+
+
+class ProfileIndex:
+    """The genes of a cohort held on one device until close() (sc_profile_index_create): uploaded once, with
+    the k-mer keys of every seed length a call has needed and the arrays the calls work in.  genes: a list of bytes.  One
+    call at a time."""
+
+    def __init__(self, genes, device=0):
+        import numpy as np
+        gl = np.array([0] + [len(x) for x in genes], dtype=np.int64).cumsum()
+        self._h = C.c_void_p()
+        rc = lib().sc_profile_index_create(int(device), b"".join(genes), gl.ctypes.data_as(C.POINTER(C.c_long)), len(genes), C.byref(self._h))
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_profile_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().sc_profile_index_free(self._h)
+            except TypeError:          # interpreter shutdown
+                pass
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def info(self):
+        """sc_profile_index_info: {"n_genes", "gene_bases", "cached_k": the seed lengths whose keys are kept, ascending}."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        n_genes, bases, n_k, ks = C.c_int(), C.c_long(), C.c_int(), (C.c_int * 6)()
+        rc = lib().sc_profile_index_info(self._h, C.byref(n_genes), C.byref(bases), C.byref(n_k), ks)
+        if rc != SC_OK:
+            raise StrainCallError(rc, lib().sc_profile_error().decode())
+        return {"n_genes": n_genes.value, "gene_bases": bases.value, "cached_k": [int(ks[i]) for i in range(n_k.value)]}
+
+    def counts(self, segs, seg_read, read_sample, n_samples, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, cap=None,
+               seeded=False, cand_room=0):
+        """sc_profile_index_counts: profile_counts over the reads of several samples at once.  segs: a list of bytes; seg_read:
+        one read index per segment; read_sample: the sample (0..n_samples-1) of every read, non-decreasing.  The room for rows
+        starts at `cap` (default 65 536) and grows to what the library asks for.  Returns a ProfileCohortCounts."""
+        import numpy as np
+        if not self._h:
+            raise ValueError("the index is closed")
+        sl = np.array([0] + [len(x) for x in segs], dtype=np.int64).cumsum()
+        stext = b"".join(segs)
+        reads = np.ascontiguousarray(seg_read, dtype=np.int32)
+        samples = np.ascontiguousarray(read_sample, dtype=np.int32)
+        if len(reads) != len(segs):
+            raise ValueError("%d read indices for %d segments" % (len(reads), len(segs)))
+        if len(reads) and int(reads.max()) >= len(samples):
+            raise ValueError("read %d of %d reads with a sample" % (int(reads.max()), len(samples)))
+        ip, lp = C.POINTER(C.c_int), C.POINTER(C.c_long)
+        cap = 1 << 16 if cap is None else int(cap)
+        while True:
+            sample, gene, times, share = (np.zeros(max(cap, 1), dtype=np.int32) for _ in range(4))
+            n_behind = np.zeros(max(cap, 1), dtype=np.int64)
+            st, n = ScProfileCohortStats(), C.c_long()
+            rc = lib().sc_profile_index_counts(self._h, stext, sl.ctypes.data_as(lp), len(segs), reads.ctypes.data_as(ip), len(samples),
+                                               samples.ctypes.data_as(ip), int(n_samples), float(min_identity), float(max_evalue),
+                                               float(ka_lambda), float(ka_k), int(bool(seeded)), int(cand_room), sample.ctypes.data_as(ip),
+                                               gene.ctypes.data_as(ip), times.ctypes.data_as(ip), share.ctypes.data_as(ip),
+                                               n_behind.ctypes.data_as(lp), cap, C.byref(n), C.byref(st))
+            if rc == -5 and n.value > cap:
+                cap = n.value
+                continue
+            if rc != SC_OK:
+                raise StrainCallError(rc, lib().sc_profile_error().decode())
+            return ProfileCohortCounts([(int(sample[i]), int(gene[i]), int(times[i]), int(share[i]), int(n_behind[i])) for i in range(n.value)],
+                                       st)
 
 
 TAXA_WORDS = 65536

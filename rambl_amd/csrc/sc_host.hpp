@@ -22,6 +22,10 @@ inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// How many device allocations DevBuf and DevMem have made on this thread: a call that wants to report what it had to set
+// aside takes the difference.
+inline thread_local long device_allocs = 0;
+
 // growable device buffer
 // A device buffer that only grows.  While regions are in flight nothing is handed back to the driver (hipFree waits for
 // the device): an outgrown buffer is kept until the worker goes; growth is geometric, so that is at most as much again --
@@ -36,7 +40,7 @@ struct DevBuf {
             if (p) { if (keep) outgrown.push_back(p); else (void)hipFree(p); }
             size_t want = keep ? std::max<size_t>(n + n / 2 + 4096, 2 * cap) : n + n / 4 + 256;
             HIPCHK(hipMalloc(&p, want));
-            cap = want;
+            cap = want; device_allocs++;
         }
         return p;
     }
@@ -113,7 +117,7 @@ template <class T> struct HostMapped {                    // host memory the dev
 };
 template <class T> struct DevMem {                        // never null: an empty array is still a device address for a kernel
     T* p = nullptr;
-    explicit DevMem(size_t n) { HIPCHK(hipMalloc((void**)&p, std::max<size_t>(n * sizeof(T), 16))); }
+    explicit DevMem(size_t n) { HIPCHK(hipMalloc((void**)&p, std::max<size_t>(n * sizeof(T), 16))); device_allocs++; }
     DevMem(const std::vector<T>& v) : DevMem(v.size()) {
         if (hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); throw HipError("hipMemcpy"); }
     }

@@ -7,7 +7,8 @@
 //   * this file              what every entry point shares -- the front end (ProfileInput: checks, packing, least passing
 //                            scores, seed length, device copies) and the score pass (ScorePass: the pair list when seeded, then
 //                            k_bl_score / k_bl_score_pairs per bucket into a candidate buffer) -- then the body of
-//                            sc_profile_hits and sc_profile_hits_seeded and the C entry points.
+//                            sc_profile_hits and sc_profile_hits_seeded and the C entry points, those of the index that keeps
+//                            the genes on the device from call to call among them (sc_profile_index_*).
 #include <cstring>
 #include <memory>
 
@@ -16,6 +17,20 @@
 namespace {
 
 thread_local LastError tl_error;
+
+// The genes of an index that outlives its calls (sc_profile_index): packed on the host and copied to the device once.
+struct ResidentGenes {
+    Packed gn;
+    sc::DevMem<uint8_t> gq;
+    sc::DevMem<long> go;
+    explicit ResidentGenes(Packed&& packed) : gn(std::move(packed)), gq(gn.codes), go(gn.off) {}
+};
+// Where a call on such an index puts its segments: arrays that grow when a call needs more and are kept otherwise.
+struct SegArena {
+    sc::DevArr<uint8_t> sq;
+    sc::DevArr<long> so;
+    sc::DevArr<int> min2;
+};
 
 // The front end of a call: the arguments every entry point takes, checked (check), packed on the host with what the score
 // pass needs per segment (prepare), and copied to the device (upload).  `fn` names the entry point in messages.
@@ -31,23 +46,33 @@ struct ProfileInput {
     bool has_len[MAX_ROWS + 1] = {};                            // the lengths of the segments that can pass
     std::vector<int> min2;                                      // min2_of_len per segment
     int seed_k = 0;                                             // the seeded mode's k; 0 runs the full product
+    template <class T> struct Ref { T* p = nullptr; };
     struct Dev {
-        sc::DevMem<uint8_t> gq, sq;                             // codes of the genes, of the segments
-        sc::DevMem<long> go, so;                                // their offsets
+        Ref<uint8_t> gq, sq;                                    // codes of the genes, of the segments
+        Ref<long> go, so;                                       // their offsets
+        Ref<int> min2;
+    };
+    struct Own {                                                // the arrays of a call that keeps nothing
+        sc::DevMem<uint8_t> gq, sq;
+        sc::DevMem<long> go, so;
         sc::DevMem<int> min2;
-        explicit Dev(const ProfileInput& in)
+        explicit Own(const ProfileInput& in)
             : gq(in.gn.codes.size()), sq(in.sg.codes.size()), go(in.gn.off.size()), so(in.sg.off.size()), min2(in.min2.size()) {}
     };
     std::unique_ptr<Dev> dev;
+    std::unique_ptr<Own> owned;
+    const ResidentGenes* resident = nullptr;                    // set: the genes are these, gene_text and gene_off are not read
 
     ProfileInput(const char* fn_, const char* gene_text_, const long* gene_off_, int n_genes_, const char* seg_text_, const long* seg_off_,
                  int n_segs_, double min_identity_pct_, double max_evalue_, double ka_lambda_, double ka_k_)
         : fn(fn_), gene_text(gene_text_), gene_off(gene_off_), n_genes(n_genes_), seg_text(seg_text_), seg_off(seg_off_), n_segs(n_segs_),
           min_identity_pct(min_identity_pct_), max_evalue(max_evalue_), ka_lambda(ka_lambda_), ka_k(ka_k_) {}
 
+    static void pack_genes(Packed& g, const char* text) { g.pack(text, [](long, int c) { return c < 0 ? REF_OTHER : c; }); }
+
     // SC_ERR_ARG unless the sequences are there, the caller's own arguments are (`own`), and the thresholds make sense
     int check(bool own) const {
-        if (!own || !gene_text || !gene_off || n_genes < 1 || n_segs < 0 || (n_segs > 0 && (!seg_text || !seg_off)))
+        if (!own || (!resident && (!gene_text || !gene_off)) || n_genes < 1 || n_segs < 0 || (n_segs > 0 && (!seg_text || !seg_off)))
             return tl_error.fail(SC_ERR_ARG, fn + ": missing argument");
         if (!(ka_lambda > 0.0) || !(ka_k > 0.0) || !(max_evalue >= 0.0))
             return tl_error.fail(SC_ERR_ARG, fn + ": lambda and K must be positive, the E-value threshold not negative");
@@ -56,10 +81,11 @@ struct ProfileInput {
 
     // The lengths checked (SC_ERR_UNSUPPORTED), the device selected (SC_ERR_NO_DEVICE, SC_ERR_HIP); then, unless there is no
     // segment, the host packing: gene and segment codes, per segment the least passing score (a segment that cannot pass even
-    // with every base matched is scored nowhere), and with `seeded` the seed length from the lengths that can pass.
+    // with every base matched is scored nowhere), and with `seeded` the seed length from the lengths that can pass.  Resident
+    // genes were checked and packed when their index was created.
     int prepare(int device, bool seeded) {
         std::string why;
-        if (!gn.rebase(gene_off, n_genes, MAX_COLS, fn.c_str(), "gene", why) ||
+        if ((!resident && !gn.rebase(gene_off, n_genes, MAX_COLS, fn.c_str(), "gene", why)) ||
             (n_segs > 0 && !sg.rebase(seg_off, n_segs, MAX_ROWS, fn.c_str(), "segment", why)))
             return tl_error.fail(SC_ERR_UNSUPPORTED, why);
         int ndev = 0;
@@ -67,9 +93,9 @@ struct ProfileInput {
         if (hipSetDevice(device) != hipSuccess) return tl_error.fail(SC_ERR_HIP, "hipSetDevice failed");
         if (n_segs == 0) return SC_OK;
         t0 = sc::now_ms();
-        gn.pack(gene_text + gene_off[0], [](long, int c) { return c < 0 ? REF_OTHER : c; });
+        if (!resident) pack_genes(gn, gene_text + gene_off[0]);
         sg.pack(seg_text + seg_off[0], [](long, int c) { return c < 0 ? 4 : c; });
-        gene_bytes = gn.bytes();
+        gene_bytes = resident ? resident->gn.bytes() : gn.bytes();
         min2.resize((size_t)n_segs);
         for (int r = 0; r < n_segs; r++) {
             const int L = (int)sg.len(r);
@@ -85,9 +111,22 @@ struct ProfileInput {
 
     // The device copies, enqueued behind the mark "upload"
     void upload(sc::TimedStream& st) {
-        dev.reset(new Dev(*this));
+        owned.reset(new Own(*this));
+        dev.reset(new Dev{{owned->gq.p}, {owned->sq.p}, {owned->go.p}, {owned->so.p}, {owned->min2.p}});
         st.mark("upload");
-        st.h2d(dev->gq, gn.codes); st.h2d(dev->go, gn.off); st.h2d(dev->sq, sg.codes); st.h2d(dev->so, sg.off); st.h2d(dev->min2, min2);
+        st.h2d(owned->gq, gn.codes); st.h2d(owned->go, gn.off);
+        upload_segments(st);
+    }
+    // The same for a call on resident genes: only the segments travel, into `arena`
+    void upload(sc::TimedStream& st, SegArena& arena) {
+        dev.reset(new Dev{{resident->gq.p}, {arena.sq.ensure(sg.codes.size() + 1)}, {resident->go.p}, {arena.so.ensure(sg.off.size())},
+                          {arena.min2.ensure(min2.size() + 1)}});
+        st.mark("upload");
+        upload_segments(st);
+    }
+    void upload_segments(sc::TimedStream& st) {
+        st.h2d(dev->sq.p, sg.codes.data(), sg.codes.size()); st.h2d(dev->so.p, sg.off.data(), sg.off.size() * sizeof(long));
+        st.h2d(dev->min2.p, min2.data(), min2.size() * sizeof(int));
     }
 };
 
@@ -97,18 +136,17 @@ struct CandBuf { Cand* p; long cap; unsigned* n; };
 // The score pass over bucketed segments (`sids` = by_r.order(), d_sids on the device), enqueued on `st` by the constructor:
 // every passing tile appends a candidate.  With an index the (segment, gene) pairs that share a k-mer are listed first
 // (seed_pairs: the stream is synchronised) and only their tiles are scored; without, the full product.  The mark "score" is
-// set in front of the kernels.  *score_cells grows by the cells of the tiles.  The pair list lives as long as this does.
+// set in front of the kernels.  *score_cells grows by the cells of the tiles.  The pair list lives in `sx`.
 struct ScorePass {
     long n_tiles = 0, n_pairs = 0;
-    sc::DevMem<Pair> pairs{0};
     ScorePass(sc::TimedStream& st, const ProfileInput& in, const Buckets& by_r, const std::vector<int>& sids, const int* d_sids,
-              const SeedIndex* index, CandBuf cand, long* score_cells) {
+              const SeedIndex* index, SeedScratch& sx, CandBuf cand, long* score_cells) {
         const ProfileInput::Dev& d = *in.dev;
         const int n_genes = in.n_genes;
         std::vector<long> pair_off(sids.size() + 1, 0);
         n_tiles = (long)sids.size() * 2L * n_genes;
         if (index) {
-            n_pairs = seed_pairs(st, *index, d.go.p, n_genes, d.sq.p, d.so.p, in.sg, by_r, sids, d_sids, in.seed_k, pair_off, pairs, score_cells);
+            n_pairs = seed_pairs(st, *index, d.go.p, n_genes, d.sq.p, d.so.p, in.sg, by_r, sids, d_sids, in.seed_k, pair_off, sx, score_cells);
             n_tiles = 2L * n_pairs;
         }
         if (n_tiles > 0x7FFFFFFFL)
@@ -120,7 +158,7 @@ struct ScorePass {
                 const long nt = 2L * (pair_off[(size_t)at + ids.size()] - pair_off[(size_t)at]);
                 if (nt == 0) return;
                 hipLaunchKernelGGL(k_bl_score_pairs<decltype(r)::value>, score_grid(nt), dim3(64 * SCORE_WAVES), 0, st, d.gq.p, d.go.p, d.sq.p, d.so.p,
-                                   PairTiles{pairs.p + pair_off[(size_t)at]}, d.min2.p, nt, cand.p, (unsigned)cand.cap, cand.n);
+                                   PairTiles{sx.pairs.get() + pair_off[(size_t)at]}, d.min2.p, nt, cand.p, (unsigned)cand.cap, cand.n);
                 st.launched();
                 return;
             }
@@ -260,7 +298,8 @@ int profile_hits(const char* fn, int device, const char* gene_text, const long* 
         st.sync();
         stats.n_gene_kmers = (long)index->n_keys;
     }
-    const ScorePass pass(st, in, by_r, sids, d_sids.p, index.get(), CandBuf{d_cand.p, cand_cap, d_ncand.p}, &stats.score_cells);
+    SeedScratch sx;
+    const ScorePass pass(st, in, by_r, sids, d_sids.p, index.get(), sx, CandBuf{d_cand.p, cand_cap, d_ncand.p}, &stats.score_cells);
     st.mark("scored");
     unsigned n_cand = 0;
     st.d2h(&n_cand, d_ncand.p, sizeof(unsigned));
@@ -295,6 +334,12 @@ int profile_hits(const char* fn, int device, const char* gene_text, const long* 
 }
 
 }  // namespace
+
+// The handle of sc_profile_index_create: what the calls on it share.  One call at a time.
+struct sc_profile_index {
+    Resident res;
+    sc_profile_index(int device, Packed&& genes) : res(device, std::move(genes)) {}
+};
 
 extern "C" {
 
@@ -342,8 +387,67 @@ int sc_profile_counts(int device, const char* gene_text, const long* gene_off, i
                       int n_segs, const int* seg_read, int n_reads, double min_identity_pct, double max_evalue, double ka_lambda,
                       double ka_k, int seeded, long cand_room, int* out_gene, int* out_times, int* out_share, long* out_reads, long cap,
                       long* n_out, sc_profile_count_stats* stats) {
-    return profile_counts(device, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, seg_read, n_reads, min_identity_pct, max_evalue,
-                          ka_lambda, ka_k, seeded, cand_room, out_gene, out_times, out_share, out_reads, cap, n_out, stats);
+    return profile_counts("sc_profile_counts", device, nullptr, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, seg_read, n_reads,
+                          Samples{nullptr, 0}, min_identity_pct, max_evalue, ka_lambda, ka_k, seeded, cand_room,
+                          RowsOut{nullptr, out_gene, out_times, out_share, out_reads, cap}, n_out, stats, nullptr);
+}
+
+int sc_profile_index_create(int device, const char* gene_text, const long* gene_off, int n_genes, sc_profile_index** out) try {
+    const std::string fn = "sc_profile_index_create";
+    tl_error.text.clear();
+    if (out) *out = nullptr;
+    if (!out || !gene_text || !gene_off || n_genes < 1) return tl_error.fail(SC_ERR_ARG, fn + ": missing argument");
+    Packed gn;
+    std::string why;
+    if (!gn.rebase(gene_off, n_genes, MAX_COLS, fn.c_str(), "gene", why)) return tl_error.fail(SC_ERR_UNSUPPORTED, why);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return tl_error.fail(SC_ERR_NO_DEVICE, "no HIP device");
+    if (hipSetDevice(device) != hipSuccess) return tl_error.fail(SC_ERR_HIP, "hipSetDevice failed");
+    ProfileInput::pack_genes(gn, gene_text + gene_off[0]);
+    *out = new sc_profile_index(device, std::move(gn));
+    return SC_OK;
+} catch (const sc::HipError&) {
+    return tl_error.fail(SC_ERR_HIP, "sc_profile_index_create: a HIP call failed");
+}
+
+int sc_profile_index_info(const sc_profile_index* index, int* n_genes, long* gene_bases, int* n_cached_k, int* cached_k) {
+    if (!index) return tl_error.fail(SC_ERR_ARG, "sc_profile_index_info: missing argument");
+    const Packed& gn = index->res.genes.gn;
+    if (n_genes) *n_genes = (int)gn.off.size() - 1;
+    if (gene_bases) *gene_bases = gn.bytes();
+    int n = 0;
+    for (int k = SEED_MIN_K; k <= SEED_MAX_K; k++) {
+        if (!index->res.seeds[k - SEED_MIN_K]) continue;
+        if (cached_k) cached_k[n] = k;
+        n++;
+    }
+    if (n_cached_k) *n_cached_k = n;
+    return SC_OK;
+}
+
+int sc_profile_index_counts(sc_profile_index* index, const char* seg_text, const long* seg_off, int n_segs, const int* seg_read, int n_reads,
+                            const int* read_sample, int n_samples, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k,
+                            int seeded, long cand_room, int* out_sample, int* out_gene, int* out_times, int* out_share, long* out_reads, long cap,
+                            long* n_out, sc_profile_cohort_stats* stats) {
+    sc_profile_cohort_stats unasked;
+    sc_profile_cohort_stats& all = stats ? *stats : unasked;
+    std::memset(&all, 0, sizeof all);
+    if (!index) return tl_error.fail(SC_ERR_ARG, "sc_profile_index_counts: missing argument");
+    const long allocs_before = sc::device_allocs;
+    Resident& res = index->res;
+    const int rc = profile_counts("sc_profile_index_counts", res.device, &res, nullptr, nullptr, (int)res.genes.gn.off.size() - 1, seg_text, seg_off,
+                                  n_segs, seg_read, n_reads, Samples{read_sample, n_samples}, min_identity_pct, max_evalue, ka_lambda, ka_k, seeded,
+                                  cand_room, RowsOut{out_sample, out_gene, out_times, out_share, out_reads, cap}, n_out, &all.counts,
+                                  &all.n_index_builds);
+    all.n_samples = n_samples;
+    all.n_allocs = sc::device_allocs - allocs_before;
+    return rc;
+}
+
+void sc_profile_index_free(sc_profile_index* index) {
+    if (!index) return;
+    (void)hipSetDevice(index->res.device);
+    delete index;
 }
 
 double sc_profile_evalue6(int L, long gene_bases, int score2, double ka_lambda, double ka_k) {

@@ -15,6 +15,7 @@ constexpr int COUNT_ROUNDS = 3;         // rounds that trace one E6 group per un
 constexpr long COUNT_ROOM = 1L << 23;   // candidate records on the device at a time unless the caller says otherwise
 constexpr int REC_BLOCKS = 256, READ_BLOCKS = 8192;     // grids: 256 threads a record each / one wavefront a read each
 constexpr int N_BUCKETS = MAX_ROWS / 64;
+constexpr int MAX_SAMPLES = 65536;      // of one call on an index
 constexpr unsigned NO_RANK = ~0u;       // in the rank table: E6 of this (length, score) is above the threshold
 constexpr int RANK_COLS = MATCH2 * MAX_ROWS + 1;        // doubled scores 0..1024
 // what the kernels count, one array of 64-bit words
@@ -189,10 +190,13 @@ __global__ __launch_bounds__(64) void k_cnt_advance(const unsigned long long* ke
 
 // One wavefront per resolved read: among the passing pairs of its group (sorted by segment, then gene) the genes hit most
 // often; one triple gene << (gene_bits + times_bits) | times << gene_bits | number of such genes per such gene goes to
-// triple[].  times[] is a word of room per record: a lane reads back only what it wrote itself.
+// triple[].  times[] is a word of room per record: a lane reads back only what it wrote itself.  With read_sample (the sample
+// of every read of the call; read r of the stretch is read0 + r there) the read's sample goes to triple_sample[] beside each
+// of its triples.
 __global__ __launch_bounds__(64) void k_cnt_count(const unsigned long long* key2, const unsigned char* state, const Cand* hit, int n_reads,
                                                   const int* cursor, const int* end, const unsigned char* resolved, int gene_bits,
-                                                  int times_bits, int* times, unsigned long long* triple, unsigned long long* ctr) {
+                                                  int times_bits, int* times, unsigned long long* triple, unsigned long long* ctr,
+                                                  const int* read_sample, int read0, int* triple_sample) {
     const int lane = threadIdx.x;
     for (int r = blockIdx.x; r < n_reads; r += gridDim.x) {
         if (resolved[r] != 1) continue;
@@ -222,13 +226,17 @@ __global__ __launch_bounds__(64) void k_cnt_count(const unsigned long long* key2
         unsigned long long base = 0;
         if (lane == 0) { base = atomicAdd(&ctr[C_TRIPLES], (unsigned long long)share); atomicAdd(&ctr[C_READS], 1ull); }
         base = __shfl(base, 0);
+        const int sample = read_sample ? read_sample[read0 + r] : 0;
         for (int j0 = c; j0 < g; j0 += 64) {
             const int j = j0 + lane;
             const bool mine = j < g && times[j] == most;
             const unsigned long long m = __ballot(mine);
-            if (mine)
-                triple[base + lanes_below(m, lane)] = ((unsigned long long)(hit[j].gene2 >> 1) << (gene_bits + times_bits)) |
-                                                      ((unsigned long long)most << gene_bits) | (unsigned long long)share;
+            if (mine) {
+                const unsigned long long at = base + lanes_below(m, lane);
+                triple[at] = ((unsigned long long)(hit[j].gene2 >> 1) << (gene_bits + times_bits)) | ((unsigned long long)most << gene_bits) |
+                             (unsigned long long)share;
+                if (read_sample) triple_sample[at] = sample;
+            }
             base += __popcll(m);
         }
     }
@@ -312,17 +320,46 @@ StretchPlan plan_stretches(const ProfileInput& in, const ReadSegs& rs, int n_rea
     return plan;
 }
 
-// What a counts call keeps on the device besides its input, set aside once per call; upload() enqueues the copies.
+// What a counts call keeps on the device besides its input, set aside once per call -- or, for a call on an index, taken from
+// the index's CountArena, which grows when a call needs more and is kept otherwise; upload() enqueues the copies.
+struct CountArena {
+    sc::DevArr<int> read, slot, sample;
+    sc::DevArr<unsigned> rank, ncand;
+    sc::DevArr<unsigned long long> ctr;
+    sc::DevArr<long> part;
+    sc::DevArr<Cand> cand;
+};
 struct CountTables {
-    sc::DevMem<int> read, slot;                                 // seg_read[], len_slot[]
-    sc::DevMem<unsigned> rank, ncand;
-    sc::DevMem<unsigned long long> ctr;                         // C_WORDS counters, zeroed per stretch
-    sc::DevMem<long> part;
-    sc::DevMem<Cand> cand;                                      // the candidate room
-    CountTables(int n_segs, const RankTable& t, long room)
-        : read((size_t)n_segs), slot(t.len_slot.size()), rank(t.rank.size()), ncand(1), ctr(C_WORDS), part(N_BUCKETS), cand((size_t)room) {}
-    void upload(sc::TimedStream& st, const int* seg_read, int n_segs, const RankTable& t) {
-        st.h2d(read.p, seg_read, (size_t)n_segs * sizeof(int)); st.h2d(slot, t.len_slot); st.h2d(rank, t.rank);
+    template <class T> using Ref = ProfileInput::Ref<T>;
+    Ref<int> read, slot;                                        // seg_read[], len_slot[]
+    Ref<int> sample;                                            // read_sample[]; null for a call that has no samples
+    Ref<unsigned> rank, ncand;
+    Ref<unsigned long long> ctr;                                // C_WORDS counters, zeroed per stretch
+    Ref<long> part;
+    Ref<Cand> cand;                                             // the candidate room
+    struct Own {
+        sc::DevMem<int> read, slot;
+        sc::DevMem<unsigned> rank, ncand;
+        sc::DevMem<unsigned long long> ctr;
+        sc::DevMem<long> part;
+        sc::DevMem<Cand> cand;
+        Own(int n_segs, const RankTable& t, long room)
+            : read((size_t)n_segs), slot(t.len_slot.size()), rank(t.rank.size()), ncand(1), ctr(C_WORDS), part(N_BUCKETS), cand((size_t)room) {}
+    };
+    std::unique_ptr<Own> own;
+    CountTables(int n_segs, const RankTable& t, long room) : own(new Own(n_segs, t, room)) {
+        read.p = own->read.p; slot.p = own->slot.p; rank.p = own->rank.p; ncand.p = own->ncand.p; ctr.p = own->ctr.p; part.p = own->part.p;
+        cand.p = own->cand.p;
+    }
+    CountTables(CountArena& a, int n_segs, int n_reads, const RankTable& t, long room) {
+        read.p = a.read.ensure((size_t)n_segs); slot.p = a.slot.ensure(t.len_slot.size()); sample.p = a.sample.ensure((size_t)n_reads);
+        rank.p = a.rank.ensure(t.rank.size()); ncand.p = a.ncand.ensure(1); ctr.p = a.ctr.ensure(C_WORDS); part.p = a.part.ensure(N_BUCKETS);
+        cand.p = a.cand.ensure((size_t)room);
+    }
+    void upload(sc::TimedStream& st, const int* seg_read, int n_segs, const RankTable& t, const int* read_sample, int n_reads) {
+        st.h2d(read.p, seg_read, (size_t)n_segs * sizeof(int)); st.h2d(slot.p, t.len_slot.data(), t.len_slot.size() * sizeof(int));
+        st.h2d(rank.p, t.rank.data(), t.rank.size() * sizeof(unsigned));
+        if (sample.p) st.h2d(sample.p, read_sample, (size_t)n_reads * sizeof(int));
     }
 };
 
@@ -342,6 +379,8 @@ struct CountBufs {
     sc::DevArr<unsigned> n_runs;
     sc::DevArr<int> first, end;                                 // a read's records in k2s / hits; first is its cursor
     sc::DevArr<unsigned char> resolved;
+    sc::DevArr<int> tsamp, tsamps, usamp;                       // a call with samples: the triples' samples as written, sorted, distinct
+    SeedScratch sx;                                             // the seeded score pass's
 };
 
 // One stretch on its way through the stages: what the host knows of it.
@@ -438,15 +477,29 @@ void trace_rounds(sc::TimedStream& st, const ProfileInput& in, const CountTables
     }
 }
 
-// The triples of the resolved reads, sorted and reduced to distinct ones (trip) with their number of reads (reads); the two
-// copies back are enqueued, not waited for.  A traceback that failed in some round shows here: SC_ERR_INTERNAL.
-void reduce_triples(sc::TimedStream& st, const ProfileInput& in, const CountTables& tb, CountBufs& b, int gene_bits, int times_bits, StretchRun& run,
-                    std::vector<unsigned long long>& trip, std::vector<unsigned>& reads) {
+// One distinct row of a stretch: the triple, its sample (0 in a call without samples) and the reads behind it.
+struct Row {
+    int sample; unsigned long long triple; long reads;
+    bool same(const Row& o) const { return sample == o.sample && triple == o.triple; }
+    bool operator<(const Row& o) const { return sample != o.sample ? sample < o.sample : triple < o.triple; }
+};
+
+// The triples of the resolved reads, sorted and reduced to distinct ones with their number of reads, appended to `rows`; the
+// stream is synchronised.  With samples (sample_bits > 0) the sample of each triple rides beside it: a stable sort by triple,
+// then a stable sort by sample, then runs of equal (sample, triple).  A traceback that failed in some round shows here:
+// SC_ERR_INTERNAL.
+void reduce_triples(sc::TimedStream& st, const ProfileInput& in, const CountTables& tb, CountBufs& b, int gene_bits, int times_bits, int sample_bits,
+                    StretchRun& run, std::vector<Row>& rows) {
     if (!run.nv) return;
     auto* trips_in = b.trip.ensure((size_t)run.nv);
     auto* trips = b.trips.ensure((size_t)run.nv);
+    const bool by_sample = tb.sample.p != nullptr;
+    int* samp_in = by_sample ? b.tsamp.ensure((size_t)run.nv) : nullptr;
+    int* samps = by_sample ? b.tsamps.ensure((size_t)run.nv) : nullptr;
+    int* usamp = by_sample ? b.usamp.ensure((size_t)run.nv) : nullptr;
     hipLaunchKernelGGL(k_cnt_count, dim3((unsigned)std::min(run.nr, READ_BLOCKS)), dim3(64), 0, st, b.k2s.get(), b.state.get(), b.hits.get(), run.nr,
-                       b.first.get(), b.end.get(), b.resolved.get(), gene_bits, times_bits, b.times.get(), trips_in, tb.ctr.p);
+                       b.first.get(), b.end.get(), b.resolved.get(), gene_bits, times_bits, b.times.get(), trips_in, tb.ctr.p, tb.sample.p,
+                       run.s.read0, samp_in);
     st.launched();
     st.d2h(run.ctr, tb.ctr.p, sizeof run.ctr);
     st.sync();
@@ -456,61 +509,112 @@ void reduce_triples(sc::TimedStream& st, const ProfileInput& in, const CountTabl
     unsigned long long* uniq = b.k2.get();                      // the reuses named at CountBufs: both arrays are free by now and
     unsigned* runs = (unsigned*)b.from.get();                   // hold nv >= nt elements of the size needed
     unsigned* n_runs = b.n_runs.ensure(1);
-    size_t t1 = 0, t2 = 0;
-    HIPCHK(rocprim::radix_sort_keys(nullptr, t1, trips_in, trips, nt, 0, 2 * gene_bits + times_bits, st));
-    HIPCHK(rocprim::run_length_encode(nullptr, t2, trips, (unsigned)nt, uniq, runs, n_runs, st));
-    void* tmp = b.tmp.ensure(std::max(t1, t2));
-    HIPCHK(rocprim::radix_sort_keys(tmp, t1, trips_in, trips, nt, 0, 2 * gene_bits + times_bits, st));
-    HIPCHK(rocprim::run_length_encode(tmp, t2, trips, (unsigned)nt, uniq, runs, n_runs, st));
+    const int triple_bits = 2 * gene_bits + times_bits;
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    if (!by_sample) {
+        HIPCHK(rocprim::radix_sort_keys(nullptr, t1, trips_in, trips, nt, 0, triple_bits, st));
+        HIPCHK(rocprim::run_length_encode(nullptr, t2, trips, (unsigned)nt, uniq, runs, n_runs, st));
+        void* tmp = b.tmp.ensure(std::max(t1, t2));
+        HIPCHK(rocprim::radix_sort_keys(tmp, t1, trips_in, trips, nt, 0, triple_bits, st));
+        HIPCHK(rocprim::run_length_encode(tmp, t2, trips, (unsigned)nt, uniq, runs, n_runs, st));
+    } else {
+        // (trips_in, samp_in) -> by triple -> (trips, samps) -> by sample, stable -> (trips_in, samp_in) again
+        unsigned* ks_in = (unsigned*)samp_in; unsigned* ks = (unsigned*)samps;
+        const auto pairs_in = rocprim::make_zip_iterator(rocprim::make_tuple(samp_in, trips_in));
+        const auto pairs_out = rocprim::make_zip_iterator(rocprim::make_tuple(usamp, uniq));
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, t1, trips_in, trips, samp_in, samps, nt, 0, triple_bits, st));
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, t2, ks, ks_in, trips, trips_in, nt, 0, sample_bits, st));
+        HIPCHK(rocprim::run_length_encode(nullptr, t3, pairs_in, (unsigned)nt, pairs_out, runs, n_runs, st));
+        void* tmp = b.tmp.ensure(std::max(t1, std::max(t2, t3)));
+        HIPCHK(rocprim::radix_sort_pairs(tmp, t1, trips_in, trips, samp_in, samps, nt, 0, triple_bits, st));
+        HIPCHK(rocprim::radix_sort_pairs(tmp, t2, ks, ks_in, trips, trips_in, nt, 0, sample_bits, st));
+        HIPCHK(rocprim::run_length_encode(tmp, t3, pairs_in, (unsigned)nt, pairs_out, runs, n_runs, st));
+    }
     unsigned n_uniq = 0;
     st.d2h(&n_uniq, n_runs, sizeof n_uniq);
     st.sync();
-    trip.resize(n_uniq); reads.resize(n_uniq);
+    std::vector<unsigned long long> trip(n_uniq);
+    std::vector<unsigned> reads(n_uniq);
+    std::vector<int> samp(by_sample ? n_uniq : 0);
     st.d2h(trip.data(), uniq, (size_t)n_uniq * 8); st.d2h(reads.data(), runs, (size_t)n_uniq * sizeof(unsigned));
+    st.d2h(samp.data(), usamp, samp.size() * sizeof(int));
+    st.sync();
+    for (unsigned k = 0; k < n_uniq; k++) rows.push_back(Row{by_sample ? samp[k] : 0, trip[k], (long)reads[k]});
 }
 
-// The stretches' (triple, reads) merged into the caller's arrays, ascending: a read is in one stretch, so the numbers of reads
-// of equal triples add.  Returns the number of distinct triples, which may be more than the `cap` that were written.
-long merge_triples(std::vector<std::pair<unsigned long long, long>>& total, int gene_bits, int times_bits, int* out_gene, int* out_times,
-                   int* out_share, long* out_reads, long cap) {
+// The caller's arrays for the rows; sample may be null (a call without samples)
+struct RowsOut { int *sample, *gene, *times, *share; long* reads; long cap; };
+
+// The stretches' rows merged into the caller's arrays, ascending: a read is in one stretch, so the numbers of reads of equal
+// rows add.  Returns the number of distinct rows, which may be more than the `cap` that were written.
+long merge_rows(std::vector<Row>& total, int gene_bits, int times_bits, const RowsOut& out) {
     std::sort(total.begin(), total.end());
     long n = 0;
     for (size_t k = 0; k < total.size(); k++) {
-        if (k > 0 && total[k].first == total[k - 1].first) { if (n <= cap) out_reads[n - 1] += total[k].second; continue; }
-        if (n < cap) {
-            out_gene[n] = (int)(total[k].first >> (gene_bits + times_bits));
-            out_times[n] = (int)((total[k].first >> gene_bits) & ((1ull << times_bits) - 1ull));
-            out_share[n] = (int)(total[k].first & ((1ull << gene_bits) - 1ull));
-            out_reads[n] = total[k].second;
+        if (k > 0 && total[k].same(total[k - 1])) { if (n <= out.cap) out.reads[n - 1] += total[k].reads; continue; }
+        if (n < out.cap) {
+            if (out.sample) out.sample[n] = total[k].sample;
+            out.gene[n] = (int)(total[k].triple >> (gene_bits + times_bits));
+            out.times[n] = (int)((total[k].triple >> gene_bits) & ((1ull << times_bits) - 1ull));
+            out.share[n] = (int)(total[k].triple & ((1ull << gene_bits) - 1ull));
+            out.reads[n] = total[k].reads;
         }
         n++;
     }
     return n;
 }
 
-// The body of sc_profile_counts: the front end; once per call the rank table, the stretch plan, the uploads and the index;
-// then per stretch the score pass and the stages above; the merge.
-int profile_counts(int device, const char* gene_text, const long* gene_off, int n_genes, const char* seg_text, const long* seg_off, int n_segs,
-                   const int* seg_read, int n_reads, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, int seeded,
-                   long cand_room, int* out_gene, int* out_times, int* out_share, long* out_reads, long cap, long* n_out,
-                   sc_profile_count_stats* stats_out) try {
-    ProfileInput in("sc_profile_counts", gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct, max_evalue, ka_lambda, ka_k);
+// What an index (sc_profile_index) keeps from call to call; a call without one passes none of it.
+struct Resident {
+    int device;
+    ResidentGenes genes;
+    std::unique_ptr<SeedIndex> seeds[SEED_MAX_K - SEED_MIN_K + 1];      // per seed length a call has needed so far
+    SegArena segs;
+    CountArena tables;
+    CountBufs bufs;
+    Resident(int device_, Packed&& packed) : device(device_), genes(std::move(packed)) {}
+};
+// The samples of a call on an index: read_sample[n_reads], non-decreasing, in 0..n_samples-1
+struct Samples { const int* of_read; int n; };
+
+// The body of sc_profile_counts and sc_profile_index_counts: the front end; once per call the rank table, the stretch plan,
+// the uploads and the index (`res`: the genes are resident, the index of this k is built only when none is cached, and every
+// array comes from res; *n_index_builds counts the builds); then per stretch the score pass and the stages above; the merge.
+int profile_counts(const char* fn_name, int device, Resident* res, const char* gene_text, const long* gene_off, int n_genes, const char* seg_text,
+                   const long* seg_off, int n_segs, const int* seg_read, int n_reads, Samples samples, double min_identity_pct, double max_evalue,
+                   double ka_lambda, double ka_k, int seeded, long cand_room, const RowsOut& out, long* n_out, sc_profile_count_stats* stats_out,
+                   int* n_index_builds) try {
+    ProfileInput in(fn_name, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct, max_evalue, ka_lambda, ka_k);
+    if (res) in.resident = &res->genes;
     const std::string& fn = in.fn;
     sc_profile_count_stats unasked;
     sc_profile_count_stats& stats = stats_out ? *stats_out : unasked;
     tl_error.text.clear();
     std::memset(&stats, 0, sizeof stats);
     if (n_out) *n_out = 0;
-    if (const int rc = in.check(n_reads >= 0 && (n_segs <= 0 || seg_read) && out_gene && out_times && out_share && out_reads && cap >= 0 &&
-                                cand_room >= 0 && n_out))
+    if (const int rc = in.check(n_reads >= 0 && (n_segs <= 0 || seg_read) && (!res || out.sample) && out.gene && out.times && out.share &&
+                                out.reads && out.cap >= 0 && cand_room >= 0 && n_out && (!res || n_reads == 0 || samples.of_read)))
         return rc;
     for (int r = 0; r < n_segs; r++)
         if (seg_read[r] < 0 || seg_read[r] >= n_reads)
             return tl_error.fail(SC_ERR_ARG, fn + ": segment " + std::to_string(r) + " belongs to read " + std::to_string(seg_read[r]) + " of " +
                                                  std::to_string(n_reads));
+    if (res) {
+        if (samples.n < 1 || samples.n > MAX_SAMPLES)
+            return tl_error.fail(SC_ERR_ARG, fn + ": " + std::to_string(samples.n) + " samples (1.." + std::to_string(MAX_SAMPLES) + " supported)");
+        for (int r = 0; r < n_reads; r++) {
+            const int s = samples.of_read[r];
+            if (s < 0 || s >= samples.n)
+                return tl_error.fail(SC_ERR_ARG, fn + ": read " + std::to_string(r) + " belongs to sample " + std::to_string(s) + " of " +
+                                                     std::to_string(samples.n));
+            if (r > 0 && s < samples.of_read[r - 1])
+                return tl_error.fail(SC_ERR_ARG, fn + ": read " + std::to_string(r) + " belongs to sample " + std::to_string(s) + " after sample " +
+                                                     std::to_string(samples.of_read[r - 1]) + ": the samples come one after the other");
+        }
+    }
     if (const int rc = in.prepare(device, seeded != 0); rc != SC_OK || n_segs == 0) return rc;
     const ReadSegs rs(seg_read, n_segs, n_reads);
-    const int gene_bits = bits_of(n_genes), times_bits = bits_of(rs.most_segs);
+    const int gene_bits = bits_of(n_genes), times_bits = bits_of(rs.most_segs), sample_bits = res ? bits_of(samples.n) : 0;
     if (2 * gene_bits + times_bits > 64)
         return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(n_genes) + " genes and " + std::to_string(rs.most_segs) +
                                                      " segments in one read do not fit a 64-bit triple");
@@ -520,22 +624,31 @@ int profile_counts(int device, const char* gene_text, const long* gene_off, int 
     const long room = plan.room;
     if (room > 0x7FFFFFFFL)
         return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(room) + " (segment, gene, strand) tiles in one read (at most 2147483647)");
-    std::vector<std::pair<unsigned long long, long>> total;     // (triple, reads) of every stretch
+    std::vector<Row> total;                                     // the rows of every stretch
     if (!plan.stretches.empty()) {
-        CountTables tb(n_segs, table, room);
-        std::unique_ptr<SeedIndex> index;
+        std::unique_ptr<CountTables> own_tb(res ? new CountTables(res->tables, n_segs, n_reads, table, room) : new CountTables(n_segs, table, room));
+        CountTables& tb = *own_tb;
+        std::unique_ptr<SeedIndex> own_index;
+        const SeedIndex* index = nullptr;
         {
             sc::TimedStream st;
-            in.upload(st);
-            tb.upload(st, seg_read, n_segs, table);
+            if (res) in.upload(st, res->segs); else in.upload(st);
+            tb.upload(st, seg_read, n_segs, table, samples.of_read, n_reads);
             st.mark("index");
-            if (in.seed_k) index.reset(new SeedIndex(st, in.dev->gq.p, in.dev->go.p, n_genes, in.gene_bytes, in.seed_k));
+            std::unique_ptr<SeedIndex>* cached = res && in.seed_k ? &res->seeds[in.seed_k - SEED_MIN_K] : nullptr;
+            if (in.seed_k && !(cached && *cached)) {
+                own_index.reset(new SeedIndex(st, in.dev->gq.p, in.dev->go.p, n_genes, in.gene_bytes, in.seed_k));
+                if (n_index_builds) ++*n_index_builds;
+            }
             st.mark("indexed");
             st.sync();
+            if (cached && own_index) { own_index->trim(); *cached = std::move(own_index); }     // kept only once it is complete
+            index = cached ? cached->get() : own_index.get();
             stats.upload_ms += st.ms("upload", "index"); stats.index_ms += st.ms("index", "indexed");
             if (index) stats.n_gene_kmers = (long)index->n_keys;
         }
-        CountBufs bufs;
+        CountBufs own_bufs;
+        CountBufs& bufs = res ? res->bufs : own_bufs;
         for (const Stretch& s : plan.stretches) {
             sc::TimedStream st;
             const Buckets by_r = rs.buckets(in, s.read0, s.read1);
@@ -546,7 +659,7 @@ int profile_counts(int device, const char* gene_text, const long* gene_off, int 
             st.zero(tb.ncand.p, sizeof(unsigned));
             st.zero(tb.ctr.p, C_WORDS * sizeof(unsigned long long));
             st.mark("lookup");
-            const ScorePass pass(st, in, by_r, sids, d_sids, index.get(), CandBuf{tb.cand.p, room, tb.ncand.p}, &stats.score_cells);
+            const ScorePass pass(st, in, by_r, sids, d_sids, index, bufs.sx, CandBuf{tb.cand.p, room, tb.ncand.p}, &stats.score_cells);
             st.mark("select");
             unsigned n_cand = 0;
             st.d2h(&n_cand, tb.ncand.p, sizeof(unsigned));
@@ -557,26 +670,23 @@ int profile_counts(int device, const char* gene_text, const long* gene_off, int 
             select_hits(st, in, tb, bufs, n_cand, run);
             trace_rounds(st, in, tb, bufs, run, stats);
             st.mark("count");
-            std::vector<unsigned long long> trip;
-            std::vector<unsigned> reads;
-            reduce_triples(st, in, tb, bufs, gene_bits, times_bits, run, trip, reads);
+            reduce_triples(st, in, tb, bufs, gene_bits, times_bits, sample_bits, run, total);
             st.mark("counted");
             st.sync();
-            for (size_t k = 0; k < trip.size(); k++) total.emplace_back(trip[k], (long)reads[k]);
             stats.upload_ms += st.ms("upload", "lookup"); stats.lookup_ms += st.ms("lookup", "score"); stats.score_ms += st.ms("score", "select");
             stats.select_ms += st.ms("select", "trace"); stats.trace_ms += st.ms("trace", "count"); stats.count_ms += st.ms("count", "counted");
             stats.n_reads_counted += (long)run.ctr[C_READS]; stats.n_hits += (long)run.ctr[C_HITS]; stats.trace_cells += (long)run.ctr[C_CELLS];
         }
     }
     int rc = SC_OK;
-    const long n = *n_out = merge_triples(total, gene_bits, times_bits, out_gene, out_times, out_share, out_reads, cap);
-    if (n > cap) rc = tl_error.fail(SC_ERR_CAPACITY, fn + ": " + std::to_string(n) + " triples, room for " + std::to_string(cap));
+    const long n = *n_out = merge_rows(total, gene_bits, times_bits, out);
+    if (n > out.cap) rc = tl_error.fail(SC_ERR_CAPACITY, fn + ": " + std::to_string(n) + " triples, room for " + std::to_string(out.cap));
     stats.total_ms = sc::now_ms() - in.t0;
     return rc;
 } catch (const sc::ScError& e) {
     return tl_error.fail(e.code, e.what());
 } catch (const sc::HipError&) {
-    return tl_error.fail(SC_ERR_HIP, "sc_profile_counts: a HIP call failed");
+    return tl_error.fail(SC_ERR_HIP, std::string(fn_name) + ": a HIP call failed");
 }
 
 }  // namespace

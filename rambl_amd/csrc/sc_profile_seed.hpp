@@ -180,29 +180,45 @@ struct SeedIndex {
         HIPCHK(rocprim::radix_sort_keys(tmp.p, tmp_bytes, keys.p, sorted.p, (size_t)gene_bytes, 0, 64, st));
         st.d2h(&n_keys, count.p, sizeof n_keys);
     }
+    // Once the stream was synchronised only `sorted` is read: an index that is kept lets the unsorted keys and the sort's
+    // temporary go.
+    void trim() {
+        { sc::DevMem<unsigned long long> none(0); std::swap(none.p, keys.p); }
+        { sc::DevMem<uint8_t> none(0); std::swap(none.p, tmp.p); }
+    }
+};
+
+// What seed_pairs sets aside on the device, kept by its owner from one score pass to the next: the per-segment counts and
+// offsets and the pair list.
+struct SeedScratch {
+    sc::DevArr<unsigned> cnt;
+    sc::DevArr<long> glen, poff;
+    sc::DevArr<Pair> pairs;
 };
 
 // The (segment, gene) pairs of the bucketed segments `sids` (d_sids on the device) that share a k-mer of the index: counted
 // per segment, scanned on the host into pair_off[sids.size() + 1], and -- unless their tiles are more than one call takes --
-// filled into `pairs` in bucket order, genes ascending.  *score_cells (may be null) grows by 2 * segment length * gene length
+// filled into sx.pairs in bucket order, genes ascending.  *score_cells (may be null) grows by 2 * segment length * gene length
 // per pair.  Returns the number of pairs; the stream is synchronised.
 long seed_pairs(sc::TimedStream& st, const SeedIndex& index, const long* d_go, int n_genes, const uint8_t* d_sq, const long* d_so,
                 const Packed& sg, const Buckets& by_r, const std::vector<int>& sids, const int* d_sids, int seed_k, std::vector<long>& pair_off,
-                sc::DevMem<Pair>& pairs, long* score_cells) {
-    sc::DevMem<unsigned> d_cnt(sids.size());
-    sc::DevMem<long> d_glen(sids.size()), d_poff(pair_off.size());
+                SeedScratch& sx, long* score_cells) {
+    unsigned* d_cnt = sx.cnt.ensure(sids.size() + 1);
+    long* d_glen = sx.glen.ensure(sids.size() + 1);
+    long* d_poff = sx.poff.ensure(pair_off.size());
+    Pair* d_pairs = sx.pairs.get();
     const auto lookup = [&](auto fill) {
         by_r.each([&](auto, long at, const std::vector<int>& ids) {
             hipLaunchKernelGGL(k_seed_lookup<decltype(fill)::value>, dim3((unsigned)std::min<size_t>(ids.size(), LOOKUP_BLOCKS)), dim3(64), 0, st,
                                index.sorted.p, (long)index.n_keys, d_go, n_genes, d_sq, d_so, d_sids + at, (int)ids.size(), seed_k,
-                               d_cnt.p + at, d_glen.p + at, d_poff.p + at, pairs.p);
+                               d_cnt + at, d_glen + at, d_poff + at, d_pairs);
             st.launched();
         });
     };
     lookup(std::false_type{});
     std::vector<unsigned> cnt(sids.size());
     std::vector<long> glen(sids.size());
-    st.d2h(cnt, d_cnt); st.d2h(glen, d_glen);
+    st.d2h(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned)); st.d2h(glen.data(), d_glen, glen.size() * sizeof(long));
     st.sync();
     for (size_t k = 0; k < sids.size(); k++) {
         pair_off[k + 1] = pair_off[k] + cnt[k];
@@ -210,10 +226,10 @@ long seed_pairs(sc::TimedStream& st, const SeedIndex& index, const long* d_go, i
     }
     const long n_pairs = pair_off.back();
     if (2L * n_pairs > 0x7FFFFFFFL || n_pairs == 0) return n_pairs;
-    { sc::DevMem<Pair> room((size_t)n_pairs); std::swap(room.p, pairs.p); }
-    st.h2d(d_poff, pair_off);
+    d_pairs = sx.pairs.ensure((size_t)n_pairs);
+    st.h2d(d_poff, pair_off.data(), pair_off.size() * sizeof(long));
     lookup(std::true_type{});
-    st.sync();                                                  // the counters go with this scope
+    st.sync();                                                  // pair_off goes with the caller's scope
     return n_pairs;
 }
 

@@ -11,6 +11,10 @@ data_info file stay valid); the reads aligned to the seed genes are SAM text, to
 has a BAM (stage4.py); `GeneTax` may be absent (the reference raises NameError then); a missing key or file is reported
 before any GPU work; the alignment files of `BamFiles` are read once and serve stages 1 and 4; the exit status tells
 whether the result is whole (0), a region failed or no seed gene was found (1), or the input was unusable (2).
+
+--profile adds what the reference leaves to a script per sample: after the length filter the samples of `BamFiles` are
+profiled against the assembled genes (cohort.cohort_profile) into <prefix>_profile/.  The alignment files
+are read a second time for it: the profile needs SEQ of every mapped record, which stages 1 and 4 do not keep.
 """
 import logging
 import os
@@ -97,6 +101,12 @@ def build_parser():
     ap.add_argument("-R", dest="keep", action="store_true", default=False, help="keep intermediate files")
     ap.add_argument("-v", dest="verbose", action="store_true", default=False, help="verbose output")
     ap.add_argument("--device", help="the GPU to run on [0]", default=0, type=int, dest="device", metavar="N")
+    # (absent from the parsed options unless given: what rambl.py's own argv parses to stays what it was)
+    ap.add_argument("--profile", dest="profile", action="store_true", default=argparse.SUPPRESS,
+                    help="after the assembly, count the reads of every sample per assembled gene: <prefix>_profile/ with one table per "
+                         "sample (named after its file) and the sample x gene matrix")
+    ap.add_argument("--profile-seeded", dest="profile_seeded", action="store_true", default=argparse.SUPPRESS,
+                    help="with --profile: score only the (segment, gene) pairs that share a k-mer (the same tables, less work)")
     return ap
 
 
@@ -121,6 +131,11 @@ def make_work_dir(parent):
             return d
         except FileExistsError:
             continue
+
+
+def profile_dir(result):
+    """<prefix>_profile next to <prefix>.fa"""
+    return os.path.splitext(result)[0] + "_profile"
 
 
 def _write(path, text):
@@ -184,6 +199,14 @@ def run(opts, data, bams, cwd=None):
                                                 opts=stage5_opts(opts), device=opts.device, streams=streams, ingest_workers=workers,
                                                 errors=errors))
         _write(result, stage5.seqtk_L(full, 400))               # rambl.py:236-238
+        if getattr(opts, "profile", False):
+            if os.path.getsize(result) == 0:
+                logging.info("no assembled gene is left in %s: the samples are not profiled", result)
+            else:
+                from . import cohort
+                timed("profile the samples",
+                      lambda: cohort.cohort_profile(result, cohort.sample_names(bams), profile_dir(result), device=opts.device,
+                                                    seeded=getattr(opts, "profile_seeded", False), verbose=opts.verbose))
         return (1 if errors else 0), times, work
     finally:
         if old_threads is None:
@@ -197,11 +220,17 @@ def run(opts, data, bams, cwd=None):
 def main(argv=None):
     """`python -m rambl_amd.pipeline DATA [options]` = `bin/rambl DATA [options]`: the argv of rambl.py."""
     t_start = time.time()
-    opts = build_parser().parse_args(argv)
+    ap = build_parser()
+    opts = ap.parse_args(argv)
+    if getattr(opts, "profile_seeded", False) and not getattr(opts, "profile", False):
+        ap.error("--profile-seeded needs --profile")
     logging.basicConfig(format="[%(asctime)s] %(levelname)s : %(message)s", level=logging.INFO)
     try:
         data = parse_data_info(opts.data_info)
         bams = check_data(data, opts.data_info)
+        if getattr(opts, "profile", False):                     # two samples of one name: known before any GPU work
+            from . import cohort
+            cohort.sample_names(bams)
         status, _, _ = run(opts, data, bams)
     except (ValueError, OSError, capi.StrainCallError) as e:
         sys.stderr.write("rambl: error: %s\n" % e)
