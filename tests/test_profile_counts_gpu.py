@@ -165,3 +165,58 @@ def test_command_line_counts_writes_the_same_table(tmp_path):
     with pytest.raises(SystemExit) as e:
         profile.main([fa, sams[0], "s", "--counts", "--keep-hits"])
     assert e.value.code == 2
+
+
+def test_faults_come_in_order_and_leave_nothing_behind():
+    """Which fault a call with several reports -- a missing argument before seg_read, seg_read before the genes' lengths, those
+    before the segments' -- and that a call without a segment returns nothing with zeroed statistics: through the library
+    itself, without an index and on one, and a good call on that index after the failed ones."""
+    import ctypes as C
+    import numpy as np
+    from rambl_amd import capi
+    ip, lp = C.POINTER(C.c_int), C.POINTER(C.c_long)
+    rng = random.Random(8)
+    genes = [CL.L.rand_seq(rng, 40).encode() for _ in range(2)]
+    segs = [genes[0][:30], genes[1][5:35], genes[1][10:40]]
+    long_gene, long_seg = b"A" * 8193, b"C" * 513
+
+    def call(ix, genes, segs, seg_read, with_gene=True):
+        """sc_profile_counts, or sc_profile_index_counts on ix with every read in sample 0 of 1 -> (rc, rows, message, stats)."""
+        offs = [np.array([0] + [len(s) for s in seqs], dtype=np.int64).cumsum() for seqs in (genes, segs)]
+        reads, samples = np.array(seg_read, dtype=np.int32), np.zeros(2, dtype=np.int32)
+        out = [np.zeros(8, dtype=np.int32) for _ in range(4)] + [np.zeros(8, dtype=np.int64)]
+        n = C.c_long(-1)
+        stats = capi.ScProfileCountStats() if ix is None else capi.ScProfileCohortStats()
+        C.memset(C.byref(stats), 0xFF, C.sizeof(stats))
+        head = (0, b"".join(genes), offs[0].ctypes.data_as(lp), len(genes)) if ix is None else (ix._h,)
+        who = (reads.ctypes.data_as(ip), 2) + (() if ix is None else (samples.ctypes.data_as(ip), 1))
+        rows = ([] if ix is None else [out[0].ctypes.data_as(ip)]) + [out[1].ctypes.data_as(ip) if with_gene else None] + \
+               [out[2].ctypes.data_as(ip), out[3].ctypes.data_as(ip), out[4].ctypes.data_as(lp)]
+        fn = capi.lib().sc_profile_counts if ix is None else capi.lib().sc_profile_index_counts
+        rc = fn(*head, b"".join(segs), offs[1].ctypes.data_as(lp), len(segs), *who, 95.0, 1e-10, 1.28, 0.46, 0, 0, *rows, 8, C.byref(n), C.byref(stats))
+        got = [tuple(int(a[k]) for a in out[1:]) for k in range(max(n.value, 0))]
+        return rc, n.value, got, capi.lib().sc_profile_error().decode(), stats.as_dict()
+
+    good = call(None, genes, segs, [0, 0, 1])
+    assert good[0] == 0 and good[1] == len(good[2]) > 0 and good[4]["n_stretches"] == 1
+    # without an index
+    rc, n, rows, msg, stats = call(None, genes, [], [])
+    assert rc == 0 and n == 0 and set(stats.values()) == {0}
+    rc, n, rows, msg, stats = call(None, genes + [long_gene], segs + [long_seg], [0, 0, 1, 1])
+    assert rc == -4 and "sc_profile_counts: gene 2 has 8193 bases (1..8192 supported)" in msg
+    rc, n, rows, msg, stats = call(None, genes, [segs[0], long_seg, segs[2]], [0, 0, 5])
+    assert rc == -3 and "segment 2 belongs to read 5 of 2" in msg
+    rc, n, rows, msg, stats = call(None, genes + [long_gene], segs, [0, 0, 1], with_gene=False)
+    assert rc == -3 and "sc_profile_counts: missing argument" in msg
+    # on an index: its genes were checked when it was made
+    with capi.ProfileIndex(genes) as ix:
+        rc, n, rows, msg, stats = call(ix, (), [], [])
+        assert rc == 0 and n == 0 and stats.pop("n_samples") == 1 and set(stats.values()) == {0}
+        rc, n, rows, msg, stats = call(ix, (), [segs[0], long_seg, segs[2]], [0, 0, 5])
+        assert rc == -3 and "segment 2 belongs to read 5 of 2" in msg
+        rc, n, rows, msg, stats = call(ix, (), [segs[0], long_seg, segs[2]], [0, 0, 1], with_gene=False)
+        assert rc == -3 and "sc_profile_index_counts: missing argument" in msg
+        rc, n, rows, msg, stats = call(ix, (), [segs[0], long_seg, segs[2]], [0, 0, 1])
+        assert rc == -4 and "sc_profile_index_counts: segment 1 has 513 bases (1..512 supported)" in msg
+        rc, n, rows, msg, stats = call(ix, (), segs, [0, 0, 1])
+        assert (rc, n, rows) == good[:3] and stats["n_stretches"] == 1
