@@ -333,14 +333,18 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         HIPCHK(hipMemcpyAsync((void*)jd_dev, &jd, sizeof jd, hipMemcpyHostToDevice, st));
 
         LevelParams& P = *w.Ph;
-        for (int s = 0; s < S; s++) P.sp[s] = StrainParam{slot(s), E, 1, 0, a0[s], 0.0};
+        for (int s = 0; s < S; s++) {
+            P.sp[s] = StrainParam{slot(s), E, 1, 0, a0[s], 0.0};
+            w.gp.slot[s] = (uint8_t)slot(s);
+            w.gp.lab[s] = f.labels[(size_t)E];
+        }
         LevelHdr H{};
         H.mode = MODE_SAMPLE; H.S = S; H.e0 = e0; H.e1 = E; H.Q = (int)Q; H.n_sweeps = n_sweeps;
         H.n_copy = 0; H.do_update = 0; H.seq = 1;
         std::memset(w.Rh, 0, sizeof(LevelResult));
         const LevelItem it = w.level_item(jd_dev, H, KMAX);
         const int kind = item_kind(it.kind);
-        const int done = launch_level(st, it, n_reads);      // as the walk of a single region launches its levels
+        const int done = launch_level(st, it, w.gp, n_reads);      // as the walk of a single region launches its levels
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
         const LevelResult& R = *w.Rh;

@@ -32,8 +32,8 @@ void launch_thread(hipStream_t st, const ThreadDev& d, int* pool_sorted);
 int init_graph_kernels();
 // ... and in sc_level.hip
 bool level_wants_grid(int n_reads, const LevelHdr& h);
-int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const LevelParams* P, LevelResult* R, bool lone);
-int launch_level(hipStream_t st, const LevelItem& it, int n_reads);
+int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const GridParams& g, const LevelParams* P, LevelResult* R, bool lone);
+int launch_level(hipStream_t st, const LevelItem& it, const GridParams& g, int n_reads);
 int level_kind(const LevelHdr& h);
 int level_lds_kb(const LevelHdr& h, int K);
 int level_table_capacity();
@@ -233,13 +233,14 @@ struct Worker {
     size_t ev_used = 0;
     LevelParams* Ph = nullptr;        // host-mapped: written here, read by the level's kernel over PCIe
     LevelParams* Pm = nullptr;        //   its device address
+    GridParams gp{};                  // beside Ph: what the grid kernels of the level take as kernel arguments, filled with Ph->sp / copy_*
     LevelParams* Pd = nullptr;        // device copy, only for the grid kernels of very large levels in a context of several regions
     LevelResult* Rh = nullptr;        // host-mapped, written by the kernel, stamped last
     LevelResult* Rd = nullptr;
     bool own_blocks = false;          // Ph / Pd / Rh are this worker's own allocations (a private worker: init_private)
     unsigned seq = 0;                 // stamp of the last level launched (the level server waits for it)
     DevBuf b_ent_rid, b_ent_cn, b_ent_lab_off, b_ent_lab_len, b_ent_first, b_ent_qoff, b_labels, b_mate_ptr, b_mate_idx,
-        b_ll, b_has, b_isnew, b_tabA, b_tabLf, b_qcode, b_qent, b_quid, b_dlog, b_out_ptr, b_out_node, b_pool_ptr, b_pool_rid,
+        b_ll, b_has, b_isnew, b_tabA, b_tabLf, b_qcode, b_qent, b_quid, b_qrid, b_dlog, b_out_ptr, b_out_node, b_pool_ptr, b_pool_rid,
         b_pool_cn, b_isend, b_esrc, b_support, b_jobdev;
     DevBuf m_seqs, m_off, m_cols0, m_cols1, m_counts, m_moves, m_trace, m_out, m_edge;
     PinnedArena* stage = nullptr;     // page-locked staging of the region's uploads / downloads: leased from the context

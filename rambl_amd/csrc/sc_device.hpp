@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <type_traits>
 
@@ -48,7 +49,15 @@ struct JobDev {
     long qcap;
     uint8_t* dlog;               // [dlog_cap] draw log of the sampler: the strain of draw t (rewritten every level)
     long dlog_cap;               // the largest n_sweeps * Q of the region's levels
+    int* qrid;                   // [qcap] read id of a draw slot (ent_rid of its entry: one dependent load less for k_level_rows);
+                                 // behind the fields the urn chain reads, whose offsets (and scalar loads) stay what they were
 };
+// The urn chain reads JobDev through scalar loads that the compiler repeats in its pass loop; with qcap, dlog and dlog_cap
+// eight bytes further on, urn_chains measured 6 ms per step slower (profiles/level_latency; observed, not yet explained:
+// DESIGN section 8).  A new field goes behind qrid, and whoever moves these measures the chain again.
+static_assert(offsetof(JobDev, quid) == 168 && offsetof(JobDev, qcap) == 176 && offsetof(JobDev, dlog) == 184 &&
+              offsetof(JobDev, dlog_cap) == 192 && offsetof(JobDev, qrid) == 200 && sizeof(JobDev) == 208,
+              "the fields the urn chain reads keep their offsets; new fields go last");
 
 // The region's block in device memory: its JobDev, written once per region, and behind it the 100 MHz tick at which the
 // first kernel of the current level began, when that is a grid kernel in front of the level's own on the same stream
@@ -88,6 +97,18 @@ struct LevelParams {
     StrainParam sp[MAXS];
     double lpt[MAXS * KK];       // log sub(a,b) - log comp(a): compact [S][K][K], K = JobDev::K
 };
+
+// What the grid kernels in front of a level (k_level_copy / update / entries / rows) need per strain, by value in their
+// kernel-argument segment: no read over PCIe stands in front of their loads.  The host fills it where it fills
+// LevelParams (LevelWalk::run_level, sc_sample_level).  A row of the read log-likelihood matrix and a symbol code are
+// both below 256: the region's builder hands out rows 0 .. MAXS - 1, a label holds codes up to KMAX (N).
+struct GridParams {
+    uint8_t slot[MAXS];          // StrainParam::slot
+    uint8_t lab[MAXS];           // first symbol of the strain's node label (read by the single-symbol update only)
+    uint8_t copy_src[MAXS], copy_dst[MAXS];
+};
+static_assert(MAXS - 1 <= UINT8_MAX && KMAX <= UINT8_MAX, "a row index and a symbol code fit GridParams' bytes");
+static_assert(sizeof(GridParams) == 4 * MAXS, "GridParams is packed");
 
 // The kind of a level names the kernel variant that serves it.  0: no sampler (k_level).  2 * NB - 1 + L, 1..16: the sampler
 // for NB = ceil(S / 16) = 1..8 register blocks per lane of a quad, L = 1 when its weight rows fit in LDS (0: they live in

@@ -209,6 +209,7 @@ __device__ __forceinline__ void phase_slots(const JD& job, const LevelHdr& h, in
             const int k = cn - 1 - i;
             const int uid = (k < mn) ? job.mate_idx[mb + k] : -1;
             job.qent[qb + i] = r;
+            job.qrid[qb + i] = rid;
             job.quid[qb + i] = uid;
             job.qcode[qb + i] = code;
         }
@@ -289,24 +290,52 @@ __device__ __forceinline__ void strain_sums(const double* prow, const uint8_t* q
 // with its own 128-byte line from the L2, 3.3 MB per level of 860 read copies x 30 strains at the 64 bytes a clock a
 // compute unit gets -- 25 us, the longest part of a level outside the chain.)  Up to 32 strains the cells stay in
 // registers between the maximum and the exponentials; beyond, they are read a second time (from the L1 / L2).
+// The rules of a row, stated once for the one-lane walk below and the lanes of a group in k_level_rows:
+// the cell x_s of a draw slot (the read's and its mate's log-likelihood, each only when present in read_loglik), ...
+struct SlotCells {
+    const double* ll; long lstride; int rid, uid; bool hr, hu;
+    __device__ __forceinline__ double operator()(int row) const {
+        const double* r = ll + (long)row * lstride;
+        double v = hr ? r[rid] : 0.0;
+        if (hu) v += r[uid];
+        return v;
+    }
+};
+template <class JD>
+__device__ __forceinline__ SlotCells slot_cells(const JD& job, const LevelHdr& h, int rid, int uid) {
+    const bool hr = h.do_update ? true : job.has[rid] != 0;      // the update has just entered the level's reads
+    const bool hu = uid >= 0 && job.has[uid] != 0;
+    return SlotCells{job.ll, job.ll_stride, rid, uid, hr, hu};
+}
+// ... the slot whose maximum m lies in the underflow range of the reference's exp() (also NaN / -inf), ...
+__device__ __forceinline__ bool row_flagged(double m) { return !(m >= -600.0); }
+// ... four neighbouring floats of its row from strain s0 on, out of the cells x[0..3]: weights (NaN when flagged) of the
+// strains below S, zeros behind them, ...
+__device__ __forceinline__ f4v row_block(const double* x, int s0, int S, double m, bool flag) {
+    const float qnanf = __int_as_float(0x7fc00000);
+    f4v w;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float wk = s0 + k < S ? (flag ? qnanf : exp_weight(x[k] - m)) : 0.0f;
+        if (k == 0) w.x = wk; else if (k == 1) w.y = wk; else if (k == 2) w.z = wk; else w.w = wk;
+    }
+    return w;
+}
+// ... and the 16 zeros at `end`, behind the last row: the chain reads whole 16-strain blocks, what follows stays finite.
+template <class PUT>
+__device__ __forceinline__ void row_tail(PUT put4, long end, int first, int step) {
+    for (int i = first; i < 4; i += step) put4(end + 4 * i, f4v{0.0f, 0.0f, 0.0f, 0.0f});
+}
+
 template <int NB, class JD, class PUT>
 __device__ __forceinline__ void weight_rows(const JD& job, const LevelHdr& h, const int* s_slot, PUT put4, int first, int step) {
     constexpr int SR = (NB <= 2) ? 16 * NB : 16;           // cells held per lane
     const int S = h.S, Q = h.Q, e0 = h.e0;
     const int stride = chain_w_stride(S);
-    const long lstride = job.ll_stride;
-    const float qnanf = __int_as_float(0x7fc00000);
     for (int q = first; q < Q; q += step) {
-        const int rid = job.ent_rid[e0 + job.qent[q]], uid = job.quid[q];
-        const bool hr = h.do_update ? true : job.has[rid] != 0;      // the update has just entered the level's reads
-        const bool hu = uid >= 0 && job.has[uid] != 0;
+        const SlotCells cells = slot_cells(job, h, job.ent_rid[e0 + job.qent[q]], job.quid[q]);
         const long Lf = (long)q * stride;
-        auto cell = [&](int sx) __attribute__((always_inline)) -> double {
-            const double* row = job.ll + (long)s_slot[sx] * lstride;
-            double v = hr ? row[rid] : 0.0;
-            if (hu) v += row[uid];
-            return v;
-        };
+        auto cell = [&](int sx) __attribute__((always_inline)) -> double { return cells(s_slot[sx]); };
         double m = -INFINITY;
         double x[SR];
         if (NB <= 2) {
@@ -318,29 +347,18 @@ __device__ __forceinline__ void weight_rows(const JD& job, const LevelHdr& h, co
                 for (int i = 0; i < SR; i++) if (s0 + i < S) m = fmax(m, cell(s0 + i));
             }
         }
-        const bool flag = !(m >= -600.0);                // underflow range of the reference's exp(); also NaN / -inf
-        // the row: S weights, the symbol, zeros up to the stride (a multiple of four floats)
+        const bool flag = row_flagged(m);
+        // the row: S weights, zeros up to the stride (a multiple of four floats)
         for (int s0 = 0; s0 < stride; s0 += SR) {
             if (NB > 2) {
 #pragma unroll
                 for (int i = 0; i < SR; i++) x[i] = (s0 + i < S) ? cell(s0 + i) : -INFINITY;
             }
 #pragma unroll
-            for (int i = 0; i < SR; i += 4) {
-                if (s0 + i < stride) {
-                    f4v w;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const int sx = s0 + i + k;
-                        const float wk = sx < S ? (flag ? qnanf : exp_weight(x[i + k] - m)) : 0.0f;
-                        if (k == 0) w.x = wk; else if (k == 1) w.y = wk; else if (k == 2) w.z = wk; else w.w = wk;
-                    }
-                    put4(Lf + s0 + i, w);
-                }
-            }
+            for (int i = 0; i < SR; i += 4)
+                if (s0 + i < stride) put4(Lf + s0 + i, row_block(x + i, s0 + i, S, m, flag));
         }
-        // the chain reads whole 16-strain blocks: keep what follows the last row finite
-        if (q == Q - 1) for (int i = 0; i < 16; i += 4) put4(Lf + stride + i, f4v{0.0f, 0.0f, 0.0f, 0.0f});
+        if (q == Q - 1) row_tail(put4, Lf + stride, 0, 1);
     }
 }
 
@@ -676,9 +694,10 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_level_resident(ResidentArgs a
 // --------------------------------------------------------------------------
 // The pieces of a level on a grid.  Each is a kernel of its own, launched in stream order in front of the level's
 // kernel: a kernel boundary is the only synchronisation between them.  They find the region through the pointer to
-// its JobDev, as the level kernels do, and the level's parameters behind P: a device copy (a very large level of a
-// context with several regions, launched from the set-up stream) or the host-mapped block itself (launch_level), of
-// which a workgroup then reads only what its own items need.  The first kernel of a level leaves its tick in JobBlock::t0.
+// its JobDev, as the level kernels do.  The strains' rows and label symbols and the copy pairs are kernel arguments
+// (GridParams); the log tables, and what k_hard_* need, lie behind P: a device copy (a very large level of a context with
+// several regions, launched from the set-up stream) or the host-mapped block itself (launch_level), of which a workgroup
+// then reads only what its own items need.  The first kernel of a level leaves its tick in JobBlock::t0.
 __device__ __forceinline__ void grid_tick(unsigned long long* t0) {
     if (t0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *t0 = wall_clock64();
 }
@@ -686,20 +705,21 @@ __device__ __forceinline__ void grid_tick(unsigned long long* t0) {
 // grid, phase 0: rows of strains created by the last extension (Strain copy, Strain.cpp:73-83); copies are
 // independent (a destination row is a free row, a source row a surviving parent's).  As in phase_copies, cells past
 // copy_n hold nothing yet.
-__global__ __launch_bounds__(256) void k_level_copy(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, unsigned long long* t0) {
+__global__ __launch_bounds__(256) void k_level_copy(const JobDev* jp, LevelHdr h, GridParams g, unsigned long long* t0) {
     grid_tick(t0);
     KJob& job = *(KJob*)jp;
     const int c = blockIdx.y;
-    const double2* src = reinterpret_cast<const double2*>(job.ll + (long)P->copy_src[c] * job.ll_stride);
-    double2* dst = reinterpret_cast<double2*>(job.ll + (long)P->copy_dst[c] * job.ll_stride);
+    const double2* src = reinterpret_cast<const double2*>(job.ll + (long)g.copy_src[c] * job.ll_stride);
+    double2* dst = reinterpret_cast<double2*>(job.ll + (long)g.copy_dst[c] * job.ll_stride);
     const int n2 = ((h.copy_n < job.n_reads ? h.copy_n : job.n_reads) + 1) >> 1;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 // grid, phase 1, single-symbol labels: ll[s][rid] (+)= log P(read symbol | strain symbol), NonparametricClustering.cpp:343-391.
-// Item idx is (strain idx / Rn, entry idx % Rn); a workgroup takes a run of consecutive items and stages the slots,
-// labels and table rows of the strains of that run alone.
-__global__ __launch_bounds__(256) void k_level_update(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, unsigned long long* t0) {
+// Item idx is (strain idx / Rn, entry idx % Rn); a workgroup takes a run of consecutive items and stages the rows, labels
+// and table rows of the strains of that run alone.  The strains' rows and symbols are kernel arguments (g), so the table
+// rows behind P (over PCIe for a lone region) are one round trip: no address waits for a value from there.
+__global__ __launch_bounds__(256) void k_level_update(const JobDev* jp, LevelHdr h, GridParams g, const LevelParams* __restrict__ P, unsigned long long* t0) {
     __shared__ double s_row[MAXS * KMAX];       // lpt[s][label of s][b]
     __shared__ double s_diag[MAXS * KMAX];      // lpt[s][b][b]  (an N in the strain label matches the read symbol)
     __shared__ int s_slot[MAXS], s_lab[MAXS];
@@ -712,8 +732,8 @@ __global__ __launch_bounds__(256) void k_level_update(const JobDev* jp, LevelHdr
     const long lo = (long)blockIdx.x * per, hi = lo + per < total ? lo + per : total;
     if (lo >= hi) return;                                   // (the whole workgroup)
     const int sa = (int)(lo / Rn), sb = (int)((hi - 1) / Rn);
-    for (int s = sa + tid; s <= sb; s += nt) { s_slot[s] = P->sp[s].slot; s_lab[s] = job.labels[P->sp[s].lab_off]; }
-    __syncthreads();
+    for (int s = sa + tid; s <= sb; s += nt) { s_slot[s] = g.slot[s]; s_lab[s] = g.lab[s]; }
+    __syncthreads();                                        // s_lab is the one source of a strain's symbol from here on
     for (int i = sa * KMAX + tid; i < (sb + 1) * KMAX; i += nt) {
         const int sx = i / KMAX, b = i % KMAX, a = s_lab[sx];
         const double* lp = P->lpt + (long)sx * K * K;                  // compact [K][K] table of the strain
@@ -748,18 +768,59 @@ __global__ __launch_bounds__(256) void k_level_entries(const JobDev* jp, LevelHd
     if (slots) phase_slots<false>(job, h, first, step);
 }
 
-// grid, phase 3: the sampler's weight rows (weight_rows) into tabLf, whichever variant of the level's kernel follows: one
-// that keeps its rows in LDS copies them from there.  A wavefront per workgroup, a draw slot per lane.
+// grid, phase 3: the sampler's weight rows into tabLf, bitwise what weight_rows writes, whichever variant of the level's
+// kernel follows: one that keeps its rows in LDS copies them from there.  A wavefront per workgroup; a group of ROWS_G
+// neighbouring lanes takes one draw slot.  Lane k of the group owns the row's blocks of four floats k, k + ROWS_G, ... (the
+// cells of four neighbouring strains each, one 16-byte store; the group's stores of a round are 16 * ROWS_G neighbouring bytes).
+// Neighbouring groups are neighbouring reads, so a load instruction is ROWS_G strains' rows at 64 / ROWS_G nearby read ids: whichever
+// strains a lane owns, a wavefront touches the same lines of the same S rows, so the layout is chosen by the stores.  The
+// cells stay in registers between the maximum and the exponentials for every NB (4 * (NB + 1) at most).  The group joins its
+// maxima with fmax, which is exact, associative and passes over a NaN on either side: m and the flag are the one-lane
+// walk's, and an empty share (S < 4 * ROWS_G) contributes -inf.  The slot's read id comes from qrid (phase_slots), the
+// strains' rows from the kernel arguments: nothing here waits for a read over PCIe.
+constexpr int ROWS_G = 8;      // measured against 4: profiles/level_latency
 template <int NB>
-__global__ __launch_bounds__(64) void k_level_rows(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, unsigned long long* t0) {
-    __shared__ int s_slot[MAXS];
+__global__ __launch_bounds__(64) void k_level_rows(const JobDev* jp, LevelHdr h, GridParams g, unsigned long long* t0) {
+    constexpr int NBLK = (4 * NB + 1 + ROWS_G - 1) / ROWS_G;      // blocks of a lane: the stride is at most 16 * NB + 4 floats
+    static_assert(64 % ROWS_G == 0 && ROWS_G <= 8, "a group lies inside a wavefront");
     grid_tick(t0);
     KJob& job = *(KJob*)jp;
-    for (int s = threadIdx.x; s < h.S; s += blockDim.x) s_slot[s] = P->sp[s].slot;
-    __syncthreads();
+    const int S = h.S, Q = h.Q;
+    const int stride = chain_w_stride(S), nblk = stride >> 2;
+    const int k = threadIdx.x % ROWS_G;
     SC_GLOBAL float* rows_g = (SC_GLOBAL float*)job.tabLf;
-    weight_rows<NB>(job, h, s_slot, [&](long idx, f4v v) __attribute__((always_inline)) { *(SC_GLOBAL f4v*)(rows_g + idx) = v; },
-                    blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    auto put4 = [&](long idx, f4v v) __attribute__((always_inline)) { *(SC_GLOBAL f4v*)(rows_g + idx) = v; };
+    // (every lane of a wavefront goes round as often as its first group: the shuffles below are the whole wavefront's)
+    const int per_wave = 64 / ROWS_G;
+    for (int q0 = blockIdx.x * per_wave; q0 < Q; q0 += gridDim.x * per_wave) {
+        const int q = q0 + threadIdx.x / ROWS_G;
+        const bool live = q < Q;
+        double x[NBLK][4];
+        double m = -INFINITY;
+        if (live) {
+            const SlotCells cells = slot_cells(job, h, job.qrid[q], job.quid[q]);
+#pragma unroll
+            for (int j = 0; j < NBLK; j++) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int sx = 4 * (k + ROWS_G * j) + i;
+                    x[j][i] = -INFINITY;
+                    if (sx < S) { x[j][i] = cells(g.slot[sx]); m = fmax(m, x[j][i]); }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < ROWS_G; o <<= 1) m = fmax(m, __shfl_xor(m, o));
+        if (!live) continue;
+        const bool flag = row_flagged(m);
+        const long Lf = (long)q * stride;
+#pragma unroll
+        for (int j = 0; j < NBLK; j++) {
+            const int blk = k + ROWS_G * j;
+            if (blk < nblk) put4(Lf + 4 * blk, row_block(x[j], 4 * blk, S, m, flag));
+        }
+        if (q == Q - 1) row_tail(put4, Lf + stride, k, ROWS_G);
+    }
 }
 
 // hard_clustering (NonparametricClustering.cpp:17-125) of a level with millions of (strain, draw slot) pairs on a grid --
@@ -865,9 +926,14 @@ static int grid_blocks(long n, int per, int most) {
     const long g = (n + per - 1) / per;
     return (int)(g < 1 ? 1 : (g > most ? most : g));
 }
-// The grid kernels of a level on `st`, in the order the level's workgroup keeps; P: the level's parameters as the
-// kernels read them (see above).  `lone`: the level of a context that walks a single region.
-int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const LevelParams* P, LevelResult* R, bool lone) {
+// The grid kernels of a level on `st`, in the order the level's workgroup keeps; g: the strains' rows and symbols and
+// the copy pairs, out of the host's own copy of the parameters; P: the level's parameters as the kernels read them (the
+// log tables, and everything k_hard_* need).  `lone`: the level of a context that walks a single region.
+// The arguments of k_level_update, the longest list among the grid kernels, as the kernel-argument segment lays them out:
+// each at its natural alignment, as the members of a struct; behind them up to 256 bytes of implicit arguments.
+struct GridUpdateArgs { const JobDev* job; LevelHdr h; GridParams g; const LevelParams* P; unsigned long long* t0; };
+static_assert(sizeof(GridUpdateArgs) + 256 <= 4096, "kernel-argument segment of the grid kernels");
+int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const GridParams& g, const LevelParams* P, LevelResult* R, bool lone) {
     const int S = h.S, Rn = h.e1 - h.e0;
     const long items = (long)S * Rn;
     const bool upd = h.do_update && Rn > 0;
@@ -886,12 +952,12 @@ int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const Leve
     // candidates -- tests/golden/wide_cap120 found it at 121 candidates x 1 085 reads.)
     if (h.n_copy > 0 && ((long)h.n_copy * n_reads > grid_min(GRID_COPY_WORDS) || update_on_grid || rows_on_grid)) {
         const int n = h.copy_n < n_reads ? h.copy_n : n_reads;
-        hipLaunchKernelGGL(k_level_copy, dim3(grid_blocks((n + 1) >> 1, 1024, 256), h.n_copy), dim3(256), 0, st, job, h, P, t0);
+        hipLaunchKernelGGL(k_level_copy, dim3(grid_blocks((n + 1) >> 1, 1024, 256), h.n_copy), dim3(256), 0, st, job, h, g, t0);
         t0 = nullptr;
         done |= LV_COPIES_DONE;
     }
     if (update_on_grid) {
-        hipLaunchKernelGGL(k_level_update, dim3(grid_blocks(items, 512, 1024)), dim3(256), 0, st, job, h, P, t0);
+        hipLaunchKernelGGL(k_level_update, dim3(grid_blocks(items, 512, 1024)), dim3(256), 0, st, job, h, g, P, t0);
         t0 = nullptr;
         done |= LV_ITEMS_DONE | LV_HAS_DONE;
     }
@@ -904,7 +970,8 @@ int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const Leve
     }
     if (rows_on_grid) {
         with_sampler_variant(kind, [&](auto nb, auto) {
-            hipLaunchKernelGGL((k_level_rows<decltype(nb)::value>), dim3(grid_blocks(h.Q, 64, 128)), dim3(64), 0, st, job, h, P, t0);
+            // every slot's group of lanes exists up to 4 096 wavefronts; beyond (Q <= MAX_DRAWS: 5 000), the kernel's loop goes round
+            hipLaunchKernelGGL((k_level_rows<decltype(nb)::value>), dim3(grid_blocks(h.Q, 64 / ROWS_G, 4096)), dim3(64), 0, st, job, h, g, t0);
         });
         done |= LV_ROWS_DONE;
     }
@@ -969,11 +1036,11 @@ void launch_level_batch(hipStream_t st, int kind, const LevelBatch& b, int n) {
 }
 // One level of a context that launches its own levels (a single region: Worker::complete_level, sc_sample_level): the
 // pieces that go on a grid, then the level's kernel, all on `st` in stream order.  Returns the level's LV_* bits.
-int launch_level(hipStream_t st, const LevelItem& it, int n_reads) {
+int launch_level(hipStream_t st, const LevelItem& it, const GridParams& g, int n_reads) {
     LevelBatch batch;
     batch.it[0] = it;
     LevelItem& b = batch.it[0];
-    b.h.done |= launch_level_grid(st, b.job, n_reads, b.h, item_kind(b.kind), b.P, b.R, true);
+    b.h.done |= launch_level_grid(st, b.job, n_reads, b.h, item_kind(b.kind), g, b.P, b.R, true);
     launch_level_batch(st, item_kind(b.kind), batch, 1);
     return b.h.done;
 }

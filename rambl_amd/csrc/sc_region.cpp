@@ -169,6 +169,7 @@ JobDev Worker::job_dev(PinnedArena& ar, const FlatGraph& f, const std::vector<in
     jd.qcode = (uint8_t*)b_qcode.ensure((size_t)qcap + 8);
     jd.qent = (int*)b_qent.ensure(sizeof(int) * (size_t)qcap);
     jd.quid = (int*)b_quid.ensure(sizeof(int) * (size_t)qcap);
+    jd.qrid = (int*)b_qrid.ensure(sizeof(int) * (size_t)qcap);
     jd.dlog_cap = std::max<long>(max_draws, 1);
     jd.dlog = (uint8_t*)b_dlog.ensure((size_t)jd.dlog_cap + 8);
     return jd;

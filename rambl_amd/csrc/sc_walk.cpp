@@ -254,7 +254,13 @@ struct LevelWalk {
         H.n_sweeps = n_sweeps; H.do_update = do_update ? 1 : 0;
         H.n_copy = (int)pending_copies.size();
         H.copy_n = do_update ? level_hi[(size_t)cur_level] : n_reads;
-        for (int c = 0; c < H.n_copy; c++) { P.copy_src[c] = pending_copies[c].first; P.copy_dst[c] = pending_copies[c].second; }
+        GridParams& G = w.gp;                          // the same rows, symbols and copy pairs, for the grid kernels' arguments
+        for (int c = 0; c < H.n_copy; c++) {
+            P.copy_src[c] = pending_copies[c].first; P.copy_dst[c] = pending_copies[c].second;
+            if ((unsigned)P.copy_src[c] >= (unsigned)MAXS || (unsigned)P.copy_dst[c] >= (unsigned)MAXS)
+                throw ScError(SC_ERR_INTERNAL, "a row copy names a row outside the read_loglik matrix");
+            G.copy_src[c] = (uint8_t)P.copy_src[c]; G.copy_dst[c] = (uint8_t)P.copy_dst[c];
+        }
         pending_copies.clear();
         {   // every candidate owns its row of the read log-likelihood matrix
             uint64_t seen[2] = {0, 0};
@@ -285,6 +291,8 @@ struct LevelWalk {
             sp.lab_len = sv[s].node >= 0 ? f.node_lab_len[sv[s].node] : 0;
             la_cache[s] = (sp.lab_len == 1) ? (int)f.labels[(size_t)sp.lab_off] : -1;       // the candidate's symbol, for the update after the level
             sp.pad = 0;
+            G.slot[s] = (uint8_t)sp.slot;                 // (0 .. MAXS - 1: checked above)
+            G.lab[s] = sp.lab_len >= 1 ? f.labels[(size_t)sp.lab_off] : (uint8_t)0;
             sp.a0 = (double)sv[s].abundance;
             sp.logpri = (mode == MODE_HARD) ? (double)logl(sv[s].abundance / za) : 0.0;      // the sampler takes a0 itself
             if (!do_update) continue;
@@ -312,7 +320,7 @@ struct LevelWalk {
             // a very large level: row copies / the single-symbol update on a grid, from a device copy of the parameters
             const size_t bytes = offsetof(LevelParams, lpt) + sizeof(double) * (size_t)S * K * K;
             HIPCHK(hipMemcpyAsync(w.Pd, w.Ph, bytes, hipMemcpyHostToDevice, w.st));
-            H.done = launch_level_grid(w.st, jd_dev, jd.n_reads, H, level_kind(H), w.Pd, w.Rd, false);
+            H.done = launch_level_grid(w.st, jd_dev, jd.n_reads, H, level_kind(H), w.gp, w.Pd, w.Rd, false);
             w.sync_stream();                             // the level's kernel runs on another stream
         }
         const int ms = w.mslot.load(std::memory_order_relaxed);
