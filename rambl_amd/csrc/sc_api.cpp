@@ -344,7 +344,7 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         std::memset(w.Rh, 0, sizeof(LevelResult));
         const LevelItem it = w.level_item(jd_dev, H, KMAX);
         const int kind = item_kind(it.kind);
-        const int done = launch_level(st, it, w.gp, n_reads);      // as the walk of a single region launches its levels
+        const int done = launch_level(st, it, w.gp, w.hp, n_reads);      // as the walk of a single region launches its levels
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
         const LevelResult& R = *w.Rh;

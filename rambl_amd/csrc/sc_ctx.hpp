@@ -32,8 +32,9 @@ void launch_thread(hipStream_t st, const ThreadDev& d, int* pool_sorted);
 int init_graph_kernels();
 // ... and in sc_level.hip
 bool level_wants_grid(int n_reads, const LevelHdr& h);
-int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const GridParams& g, const LevelParams* P, LevelResult* R, bool lone);
-int launch_level(hipStream_t st, const LevelItem& it, const GridParams& g, int n_reads);
+int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const GridParams& g, const HardPriors& pri,
+                      const LevelParams* P, LevelResult* R, bool lone);
+int launch_level(hipStream_t st, const LevelItem& it, const GridParams& g, const HardPriors& pri, int n_reads);
 int level_kind(const LevelHdr& h);
 int level_lds_kb(const LevelHdr& h, int K);
 int level_table_capacity();
@@ -234,6 +235,7 @@ struct Worker {
     LevelParams* Ph = nullptr;        // host-mapped: written here, read by the level's kernel over PCIe
     LevelParams* Pm = nullptr;        //   its device address
     GridParams gp{};                  // beside Ph: what the grid kernels of the level take as kernel arguments, filled with Ph->sp / copy_*
+    HardPriors hp{};                  // ... and Ph->sp[].logpri, for the hard update on the grid
     LevelParams* Pd = nullptr;        // device copy, only for the grid kernels of very large levels in a context of several regions
     LevelResult* Rh = nullptr;        // host-mapped, written by the kernel, stamped last
     LevelResult* Rd = nullptr;

@@ -109,6 +109,10 @@ struct GridParams {
 };
 static_assert(MAXS - 1 <= UINT8_MAX && KMAX <= UINT8_MAX, "a row index and a symbol code fit GridParams' bytes");
 static_assert(sizeof(GridParams) == 4 * MAXS, "GridParams is packed");
+// The strains' log priors of a hard update (StrainParam::logpri), by value in the arguments of k_hard_resp alone: 1 KB.
+struct HardPriors {
+    double logpri[MAXS];
+};
 
 // The kind of a level names the kernel variant that serves it.  0: no sampler (k_level).  2 * NB - 1 + L, 1..16: the sampler
 // for NB = ceil(S / 16) = 1..8 register blocks per lane of a quad, L = 1 when its weight rows fit in LDS (0: they live in
@@ -192,7 +196,7 @@ struct LevelResult {
     unsigned long long chain_cycles, chain_wall;   // shader cycles / 100 MHz ticks spent in the urn chain
     unsigned long long n_exact;  // draws resolved by the literal fp64 path
     unsigned long long level_wall;                 // 100 MHz ticks the GPU spent on the level: from the start of its kernel, or of the first grid kernel in front of it on the same stream (LV_TICKED)
-    unsigned phase_ticks[6];     // diagnostics: 100 MHz ticks at the end of staging / copies / update / slots / table / chain
+    unsigned phase_ticks[6];     // diagnostics: 100 MHz ticks at the end of staging / copies / update / slots / table, and (sampler levels) of the count over the draw log
     int error;
     int xcc;                     // XCD the level's workgroup ran on (HW_REG_XCC_ID)
     unsigned seq;                // == LevelHdr::seq once every other field is in place

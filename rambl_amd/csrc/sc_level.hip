@@ -373,7 +373,7 @@ __device__ __forceinline__ LevelLds level_lds(unsigned char* raw) {
     l.s_a = reinterpret_cast<double*>(raw);                        // [MAXS]
     l.s_p = l.s_a + MAXS;                                          // [MAXS]
     l.s_sp = reinterpret_cast<StrainParam*>(l.s_p + MAXS);         // [MAXS]
-    l.s_cnt = reinterpret_cast<unsigned*>(l.s_sp + MAXS);          // [MAXS*KMAX]
+    l.s_cnt = reinterpret_cast<unsigned*>(l.s_sp + MAXS);          // [KMAX*MAXS], log_cnt_index
     l.s_slot = reinterpret_cast<int*>(l.s_cnt + MAXS * KMAX);      // [MAXS]
     l.s_kf = reinterpret_cast<unsigned*>(l.s_slot + MAXS);         // [MAXS] draws per strain so far
     l.s_a0f = reinterpret_cast<float*>(l.s_kf + MAXS);             // [MAXS] fp32 copy of the starting weights
@@ -485,7 +485,8 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
     if (!STAY) nt = 64 * NW;
     draw_log_counts(job, h, l.s_cnt, tid, nt);               // (behind the chain's closing barrier, by every wavefront still here)
     __syncthreads();
-    for (int i = tid; i < S * KMAX; i += nt) R->cnt[i] = l.s_cnt[i];
+    if (tid == 0) R->phase_ticks[5] = (unsigned)(wall_clock64() - wall0);      // the count's end: what follows is stores, fence and stamp
+    for (int i = tid; i < S * KMAX; i += nt) R->cnt[i] = l.s_cnt[log_cnt_index(i / KMAX, i % KMAX)];
     finish_level(h, R, wall0, tid);
 }
 
@@ -523,7 +524,7 @@ __device__ __forceinline__ void level_plain_body(const IT& it, unsigned char* s_
     // row reads of a slot's strains are all in flight together
     for (long idx = tid; idx < (long)S * Q; idx += nt) {
         const int s = (int)(idx / Q), q = (int)(idx % Q);
-        const int rid = job.ent_rid[e0 + job.qent[q]], uid = job.quid[q];
+        const int rid = job.qrid[q], uid = job.quid[q];         // (qrid: ent_rid of the slot's entry, one dependent load less)
         const double* row = job.ll + (long)l.s_sp[s].slot * stride;
         double x = l.s_sp[s].logpri + row[rid];
         if (uid >= 0) x += row[uid];
@@ -695,9 +696,10 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_level_resident(ResidentArgs a
 // The pieces of a level on a grid.  Each is a kernel of its own, launched in stream order in front of the level's
 // kernel: a kernel boundary is the only synchronisation between them.  They find the region through the pointer to
 // its JobDev, as the level kernels do.  The strains' rows and label symbols and the copy pairs are kernel arguments
-// (GridParams); the log tables, and what k_hard_* need, lie behind P: a device copy (a very large level of a context with
-// several regions, launched from the set-up stream) or the host-mapped block itself (launch_level), of which a workgroup
-// then reads only what its own items need.  The first kernel of a level leaves its tick in JobBlock::t0.
+// (GridParams), the log priors of a hard update too (HardPriors); the log tables lie behind P: a device copy (a very large
+// level of a context with several regions, launched from the set-up stream) or the host-mapped block itself
+// (launch_level), of which a workgroup of k_level_update then reads only what its own items need.  k_hard_* read nothing
+// behind P: seven launches stand in front of a plain level of a lone region, and none of them waits for PCIe.  The first kernel of a level leaves its tick in JobBlock::t0.
 __device__ __forceinline__ void grid_tick(unsigned long long* t0) {
     if (t0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *t0 = wall_clock64();
 }
@@ -830,23 +832,23 @@ __global__ __launch_bounds__(64) void k_level_rows(const JobDev* jp, LevelHdr h,
 // (normalise_column; each side fills x and finds its maximum its own way: the workgroup spreads (strain, slot) pairs over
 // its threads, a thread of the grid walks its slot's strains); per strain ONE wavefront that adds its responsibilities
 // (strain_sums): bit-identical results, 100 CUs instead of one.
-__global__ __launch_bounds__(256) void k_hard_mates(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P) {
+__global__ __launch_bounds__(256) void k_hard_mates(const JobDev* jp, LevelHdr h, GridParams g) {
     __shared__ int s_slot[MAXS];
     KJob& job = *(KJob*)jp;
-    for (int s = threadIdx.x; s < h.S; s += blockDim.x) s_slot[s] = P->sp[s].slot;
+    for (int s = threadIdx.x; s < h.S; s += blockDim.x) s_slot[s] = g.slot[s];
     __syncthreads();
     zero_unseen_mates(job, h, [&](int s) { return s_slot[s]; }, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
-__global__ __launch_bounds__(256) void k_hard_resp(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P) {
+__global__ __launch_bounds__(256) void k_hard_resp(const JobDev* jp, LevelHdr h, GridParams g, HardPriors pri) {
     __shared__ int s_slot[MAXS];
     __shared__ double s_logpri[MAXS];
     KJob& job = *(KJob*)jp;
-    const int S = h.S, e0 = h.e0;
-    for (int s = threadIdx.x; s < S; s += blockDim.x) { s_slot[s] = P->sp[s].slot; s_logpri[s] = P->sp[s].logpri; }
+    const int S = h.S;
+    for (int s = threadIdx.x; s < S; s += blockDim.x) { s_slot[s] = g.slot[s]; s_logpri[s] = pri.logpri[s]; }
     __syncthreads();
     const long stride = job.ll_stride;
     for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < h.Q; q += gridDim.x * blockDim.x) {
-        const int rid = job.ent_rid[e0 + job.qent[q]], uid = job.quid[q];
+        const int rid = job.qrid[q], uid = job.quid[q];      // (qrid: ent_rid of the slot's entry, written with the slot)
         if (uid >= 0) job.has[uid] = 1;                      // (every check of k_hard_mates is behind us: a kernel boundary)
         double* col = job.tabA + q;
         double m = -INFINITY;
@@ -860,13 +862,14 @@ __global__ __launch_bounds__(256) void k_hard_resp(const JobDev* jp, LevelHdr h,
         normalise_column(col, job.qcap, S, m);
     }
 }
-// one wavefront per strain (= per workgroup of 64)
-__global__ __launch_bounds__(64) void k_hard_sums(const JobDev* jp, LevelHdr h, const LevelParams* __restrict__ P, LevelResult* __restrict__ R) {
+// one wavefront per strain (= per workgroup of 64); the strain's symbol is its label's only one (no multi-symbol label
+// reaches the grid)
+__global__ __launch_bounds__(64) void k_hard_sums(const JobDev* jp, LevelHdr h, GridParams g, LevelResult* __restrict__ R) {
     KJob& job = *(KJob*)jp;
     const int s = blockIdx.x, lane = threadIdx.x, K = job.K, K2 = K * K, Q = h.Q;
     double acc[KMAX + 1];
     strain_sums(job.tabA + (long)s * job.qcap, job.qcode, Q, lane, acc);
-    const int a = (int)job.labels[P->sp[s].lab_off];
+    const int a = (int)g.lab[s];
     // the strain's [K][K] block of the substitution histogram: zero except the row of its own symbol (every cell written
     // once, by the lane that owns it; the sums live in lane 0)
     double row[KMAX];
@@ -914,7 +917,7 @@ static long wide_min() {
     return forced >= 0 ? forced : WIDE_ITEMS;
 }
 static bool hard_on_grid(const LevelHdr& h) {
-    // (behind the grid's update only: the pieces of a level keep their order)
+    // (behind the grid's update only: the pieces of a level keep their order; a context with several regions)
     return h.mode == MODE_HARD && h.do_update && (long)h.S * (h.e1 - h.e0) > grid_min(GRID_ITEMS) && !h.has_dups && !h.any_multi &&
            (long)h.S * h.Q > grid_min(GRID_HARD) && h.e1 > h.e0;
 }
@@ -928,12 +931,15 @@ static int grid_blocks(long n, int per, int most) {
 }
 // The grid kernels of a level on `st`, in the order the level's workgroup keeps; g: the strains' rows and symbols and
 // the copy pairs, out of the host's own copy of the parameters; P: the level's parameters as the kernels read them (the
-// log tables, and everything k_hard_* need).  `lone`: the level of a context that walks a single region.
-// The arguments of k_level_update, the longest list among the grid kernels, as the kernel-argument segment lays them out:
-// each at its natural alignment, as the members of a struct; behind them up to 256 bytes of implicit arguments.
+// log tables); pri: the log priors of a hard update.  `lone`: the level of a context that walks a single region.
+// The arguments of k_level_update and of k_hard_resp, the longest lists among the grid kernels, as the kernel-argument
+// segment lays them out: each at its natural alignment, as the members of a struct; behind them up to 256 bytes of
+// implicit arguments.
 struct GridUpdateArgs { const JobDev* job; LevelHdr h; GridParams g; const LevelParams* P; unsigned long long* t0; };
-static_assert(sizeof(GridUpdateArgs) + 256 <= 4096, "kernel-argument segment of the grid kernels");
-int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const GridParams& g, const LevelParams* P, LevelResult* R, bool lone) {
+struct GridHardArgs { const JobDev* job; LevelHdr h; GridParams g; HardPriors pri; };
+static_assert(sizeof(GridUpdateArgs) + 256 <= 4096 && sizeof(GridHardArgs) + 256 <= 4096, "kernel-argument segment of the grid kernels");
+int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const LevelHdr& h, int kind, const GridParams& g, const HardPriors& pri,
+                      const LevelParams* P, LevelResult* R, bool lone) {
     const int S = h.S, Rn = h.e1 - h.e0;
     const long items = (long)S * Rn;
     const bool upd = h.do_update && Rn > 0;
@@ -942,7 +948,9 @@ int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const Leve
     // the weight rows read what the update writes and the `has` marks behind it: behind the grid's update, or on a level
     // without one (read_assign)
     const bool rows_on_grid = wide && kind_has_sampler(kind) && h.Q > 0 && (update_on_grid || !upd);
-    const bool hard = update_on_grid && hard_on_grid(h);
+    // the hard update behind the grid's update: a very large one in any context, and in a lone region's every one whose
+    // level went wide (255 CUs stand idle while one workgroup walks its (strain, slot) pairs: profiles/level_tail)
+    const bool hard = update_on_grid && (hard_on_grid(h) || (wide && h.mode == MODE_HARD && h.Q > 0));
     int done = 0;
     unsigned long long* t0 = lone ? &reinterpret_cast<JobBlock*>(const_cast<JobDev*>(job))->t0 : nullptr;      // for the level's first kernel
     // The rows of the level's new candidates come first, whoever makes them: a candidate's row must be its parent's row of
@@ -977,9 +985,9 @@ int launch_level_grid(hipStream_t st, const JobDev* job, int n_reads, const Leve
     }
     if (hard) {
         const int gq = grid_blocks(h.Q, 256, 2048);
-        hipLaunchKernelGGL(k_hard_mates, dim3(gq), dim3(256), 0, st, job, h, P);
-        hipLaunchKernelGGL(k_hard_resp, dim3(gq), dim3(256), 0, st, job, h, P);
-        hipLaunchKernelGGL(k_hard_sums, dim3(S), dim3(64), 0, st, job, h, P, R);
+        hipLaunchKernelGGL(k_hard_mates, dim3(gq), dim3(256), 0, st, job, h, g);
+        hipLaunchKernelGGL(k_hard_resp, dim3(gq), dim3(256), 0, st, job, h, g, pri);
+        hipLaunchKernelGGL(k_hard_sums, dim3(S), dim3(64), 0, st, job, h, g, R);
         done |= LV_HARD_DONE;
     }
     return done ? (done | (lone ? LV_TICKED : 0)) : 0;
@@ -1036,11 +1044,11 @@ void launch_level_batch(hipStream_t st, int kind, const LevelBatch& b, int n) {
 }
 // One level of a context that launches its own levels (a single region: Worker::complete_level, sc_sample_level): the
 // pieces that go on a grid, then the level's kernel, all on `st` in stream order.  Returns the level's LV_* bits.
-int launch_level(hipStream_t st, const LevelItem& it, const GridParams& g, int n_reads) {
+int launch_level(hipStream_t st, const LevelItem& it, const GridParams& g, const HardPriors& pri, int n_reads) {
     LevelBatch batch;
     batch.it[0] = it;
     LevelItem& b = batch.it[0];
-    b.h.done |= launch_level_grid(st, b.job, n_reads, b.h, item_kind(b.kind), g, b.P, b.R, true);
+    b.h.done |= launch_level_grid(st, b.job, n_reads, b.h, item_kind(b.kind), g, pri, b.P, b.R, true);
     launch_level_batch(st, item_kind(b.kind), batch, 1);
     return b.h.done;
 }

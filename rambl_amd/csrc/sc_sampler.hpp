@@ -446,43 +446,73 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
 // The draws per (strain, read symbol) -- the substitution counts of :198-206 -- out of the draw log, after the chain's
 // closing barrier, by every wavefront of the workgroup that is still there.  Draw t is the draw of slot t % Q, whose read
 // symbol is job.qcode[slot]; a symbol >= KMAX (no single symbol) is not counted.  A lane takes one slot and a stretch of
-// its sweeps (the whole column while there are more slots than lanes) and counts runs of one strain in a register: a read
-// prefers the same strain sweep after sweep, so a lane adds to s_cnt once per run, not once per draw, and the lanes of a
-// wavefront do so at different times -- no many-way conflicts on one address.  The log is rewritten every level, also by
-// a workgroup that stays on its CU (resident workers): the chain's wavefronts have drained their stores in front of the
-// barrier, and a device-scope acquire here keeps the L1 from serving a line of an earlier level.
+// at most LOG_STRETCH of its sweeps and counts runs of one strain in a register: where a read prefers one strain sweep
+// after sweep, a lane adds to s_cnt once per run, not once per draw.
+//
+// Where the time goes (profiles/level_tail): not into the loads -- a lane issues every load of its stretch, and the slot's
+// symbol beside them, before it uses the first, one round trip to the L2 per round of the loop, and that alone moved the
+// count by 0.5 us of 11.7 -- but into the LDS adds.  A level of 30 candidates that differ in one symbol each gives a read
+// nearly the same weight for all of them: runs are one or two draws long, a level has tens of thousands of adds, and the
+// slots of one level carry almost all the same symbol.  With counts laid out [strain][symbol] every add of a wavefront
+// then falls on the two banks (strain * 16 + symbol) mod 32 leaves, one LDS cycle per distinct address.  s_cnt is therefore
+// [symbol][strain] (log_cnt_index): the bank is the strain's, adds to different strains go side by side, and only lanes
+// that add to the very same strain take turns.  The level's body writes LevelResult::cnt from it in the result's order.
+//
+// A stretch shorter than the loaded blocks of eight (the slot's last stretch, or a stretch that is no multiple of eight)
+// loads its own last sweep again in place of the sweeps it does not have -- inside the log.  Those copies lengthen the
+// stretch's last run, by a number the lane knows and takes off again, so no step of the walk asks whether it exists.
+// Blocks of eight that no stretch of the level reaches are skipped by the whole workgroup.  The log is rewritten every
+// level, also by a workgroup that stays on its CU (resident workers): the chain's wavefronts have drained their stores in
+// front of the barrier, and a device-scope acquire here keeps the L1 from serving a line of an earlier level.
+constexpr int LOG_STRETCH = 24;                              // sweeps a lane holds in registers (three blocks of eight loads)
+__device__ __forceinline__ int log_cnt_index(int strain, int sym) { return sym * MAXS + strain; }     // s_cnt: [KMAX][MAXS]
 template <class JD>
 __device__ __forceinline__ void draw_log_counts(const JD& job, const LevelHdr& h, unsigned* s_cnt, int tid, int nt) {
     const int Q = h.Q, n = h.n_sweeps;
     if (Q <= 0 || n <= 0) return;                           // (no draws: uniform over the workgroup, like the chain's own loop)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const SC_GLOBAL unsigned char* dlog = (const SC_GLOBAL unsigned char*)job.dlog;
-    const int G = Q < nt ? min(nt / Q, n) : 1;              // stretches of sweeps per slot
-    const int per = (n + G - 1) / G;
-    for (int idx = tid; idx < Q * G; idx += nt) {
-        const int q = idx % Q, j0 = (idx / Q) * per, j1 = min(j0 + per, n);
-        const int sym = job.qcode[q];
-        if (sym >= KMAX || j0 >= j1) continue;
-        const SC_GLOBAL unsigned char* p = dlog + (j0 * Q + q);
-        int cur = 0;
-        unsigned run = 0;
-        auto count = [&](int c) __attribute__((always_inline)) {
-            if (c != cur) {
-                if (run) __hip_atomic_fetch_add(&s_cnt[cur * KMAX + sym], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                cur = c; run = 0;
+    const SC_GLOBAL unsigned char* qcode = (const SC_GLOBAL unsigned char*)job.qcode;
+    // stretches of sweeps per slot: as many as a stretch needs to fit the registers, more while lanes would be idle
+    const int G = max((n + LOG_STRETCH - 1) / LOG_STRETCH, min(nt / Q, n));
+    const int per = (n + G - 1) / G;                        // 1 .. LOG_STRETCH, uniform
+    const int loaded = (per + 7) & ~7;                      // sweeps a lane loads and walks: whole blocks
+    for (int idx = tid; idx < Q * G; idx += nt) {           // (Q * G <= Q * n <= JobDev::dlog_cap)
+        const int q = idx % Q, j0 = (idx / Q) * per;
+        const int len = min(per, n - j0);                   // sweeps [j0, j0 + len) of slot q
+        if (len <= 0) continue;                             // (G * per can pass n by more than a stretch)
+        const unsigned at = (unsigned)(j0 * Q + q), last = (unsigned)(len - 1);
+        int c[LOG_STRETCH];
+#pragma unroll
+        for (int b = 0; b < LOG_STRETCH; b += 8) {
+            if (b < per) {
+#pragma unroll
+                for (int i = b; i < b + 8; i++) c[i] = dlog[at + min((unsigned)i, last) * (unsigned)Q];     // byte < n * Q
+            } else {
+#pragma unroll
+                for (int i = b; i < b + 8; i++) c[i] = 0;
             }
-            run++;
-        };
-        int j = j0;
-        for (; j + 8 <= j1; j += 8, p += 8 * Q) {
-            int c[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) c[i] = p[i * Q] & (MAXS - 1);     // eight sweeps in flight (a strain index: s_cnt is [MAXS][KMAX])
-#pragma unroll
-            for (int i = 0; i < 8; i++) count(c[i]);
         }
-        for (; j < j1; j++, p += Q) count(*p & (MAXS - 1));
-        if (run) __hip_atomic_fetch_add(&s_cnt[cur * KMAX + sym], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const int sym = qcode[q];
+        if (sym >= KMAX) continue;
+        unsigned* const mine = s_cnt + log_cnt_index(0, sym);
+        int cur = c[0] & (MAXS - 1);                        // (a strain index: s_cnt has MAXS of them per symbol)
+        unsigned run = 0;
+#pragma unroll
+        for (int b = 0; b < LOG_STRETCH; b += 8) {
+            if (b >= per) break;                            // (uniform)
+#pragma unroll
+            for (int i = b; i < b + 8; i++) {
+                const int ci = c[i] & (MAXS - 1);
+                if (ci != cur) {
+                    __hip_atomic_fetch_add(&mine[cur], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    cur = ci; run = 0;
+                }
+                run++;
+            }
+        }
+        run -= (unsigned)(loaded - len);                    // the copies of the last sweep: all in the last run, which has >= 1 beside them
+        __hip_atomic_fetch_add(&mine[cur], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 }
 

@@ -427,7 +427,7 @@ void Worker::complete_level(const LevelItem& it, int n_reads, bool timed) {
         hipStream_t ls = ctx->launch->st;
         if (timed) HIPCHK(hipEventRecord(ev0, ls));
         (void)hipGetLastError();
-        level_done = launch_level(ls, it, gp, n_reads);
+        level_done = launch_level(ls, it, gp, hp, n_reads);
         { const hipError_t le = hipGetLastError(); if (le != hipSuccess) throw HipError(std::string("level kernel launch: ") + hipGetErrorString(le)); }
         if (timed) HIPCHK(hipEventRecord(ev1, ls));
         t_batch_launched = now_ms(); batch_n = 1;

@@ -295,6 +295,7 @@ struct LevelWalk {
             G.lab[s] = sp.lab_len >= 1 ? f.labels[(size_t)sp.lab_off] : (uint8_t)0;
             sp.a0 = (double)sv[s].abundance;
             sp.logpri = (mode == MODE_HARD) ? (double)logl(sv[s].abundance / za) : 0.0;      // the sampler takes a0 itself
+            w.hp.logpri[s] = sp.logpri;
             if (!do_update) continue;
             // log table of the strain: only the rows its counts changed in since the last level are redone, and in
             // them only the logarithms of the counts that changed
@@ -320,7 +321,7 @@ struct LevelWalk {
             // a very large level: row copies / the single-symbol update on a grid, from a device copy of the parameters
             const size_t bytes = offsetof(LevelParams, lpt) + sizeof(double) * (size_t)S * K * K;
             HIPCHK(hipMemcpyAsync(w.Pd, w.Ph, bytes, hipMemcpyHostToDevice, w.st));
-            H.done = launch_level_grid(w.st, jd_dev, jd.n_reads, H, level_kind(H), w.gp, w.Pd, w.Rd, false);
+            H.done = launch_level_grid(w.st, jd_dev, jd.n_reads, H, level_kind(H), w.gp, w.hp, w.Pd, w.Rd, false);
             w.sync_stream();                             // the level's kernel runs on another stream
         }
         const int ms = w.mslot.load(std::memory_order_relaxed);
@@ -352,11 +353,12 @@ struct LevelWalk {
         if (chain) stats.sampler_level_ticks += (long)Rh->level_wall;
         if (level_log) {
             const double t_done = now_ms();
-            fprintf(level_log, "h %d mode %d S %d Q %d n %d level_us %.1f chain_us %.1f cyc %llu passes %llu slow %llu xcc %d ncopy %d copyn %d multi %d done %d "
-                    "ph %.1f %.1f %.1f %.1f %.1f host_us %.1f wait_us %.1f pend_us %.1f batch %d\n", job.handle, mode, S, Q,
+            fprintf(level_log, "h %d mode %d S %d Q %d n %d level_us %.1f chain_us %.1f cyc %llu passes %llu slow %llu xcc %d ncopy %d copyn %d multi %d dups %d done %d "
+                    "ph %.1f %.1f %.1f %.1f %.1f %.1f host_us %.1f wait_us %.1f pend_us %.1f batch %d\n", job.handle, mode, S, Q,
                     n_sweeps, Rh->level_wall * 0.01, chain ? Rh->chain_wall * 0.01 : 0.0, chain ? (unsigned long long)Rh->chain_cycles : 0ull,
-                    chain ? (unsigned long long)Rh->n_pass : 0ull, chain ? (unsigned long long)Rh->n_slow : 0ull, Rh->xcc, H.n_copy, H.copy_n, (int)any_multi, w.level_done,
+                    chain ? (unsigned long long)Rh->n_pass : 0ull, chain ? (unsigned long long)Rh->n_slow : 0ull, Rh->xcc, H.n_copy, H.copy_n, (int)any_multi, (int)has_dups, w.level_done,
                     Rh->phase_ticks[0] * 0.01, Rh->phase_ticks[1] * 0.01, Rh->phase_ticks[2] * 0.01, Rh->phase_ticks[3] * 0.01, Rh->phase_ticks[4] * 0.01,
+                    chain ? Rh->phase_ticks[5] * 0.01 : 0.0,         // (the end of the count over the draw log: sampler levels only)
                     1e3 * (t_launched - t_last_done), 1e3 * (t_done - t_launched), 1e3 * (w.t_batch_launched - t_launched), w.batch_n);
             t_last_done = t_done;
         }
