@@ -1,6 +1,11 @@
 """GPU: the genus assignment on the device (rambl_amd/csrc/sc_taxa.hip) against the plain restatement of DESIGN.md §8.12 in
-tests/taxa_lib.py: counts and table cell for cell (exactly: every case keeps its cells off the half-integers), assigned
-genus and trial winners, the limits, and the command lines byte for byte."""
+tests/taxa_lib.py: counts and table cell for cell (exactly, against the table computed with mpmath: every case keeps its
+cells beyond the fp64 error bound of a half-integer, and one case puts cells within 1e-7 of one), assigned genus and trial
+winners, the limits, and the command lines byte for byte.  The named edge cases of the word, table and score kernels are
+in taxa_lib with their property checks.
+
+Not reached: the second batch of sc_taxa_classify (q0 > 0).  A batch holds PART_ROOM = 2^25 (query, chunk, slot) records, so
+a second one needs some 16 384 genera, a 4 GiB table, while PART_ROOM is a constant of the library."""
 import os
 
 import numpy as np
@@ -129,6 +134,156 @@ def test_limits():
         assert ei.value.code == -4
         best, winners, words, _ = dev.classify([b"ACGTACGTAC"], [1])
         assert int(best[0]) == 0 and int(words[0]) == 3
+        with pytest.raises(capi.StrainCallError) as ei:
+            dev.classify([b"ACGTACGTAC"], [1], n_trials=1025)
+        assert ei.value.code == -4 and "1025 trials (1..1024 supported)" in str(ei.value)
+        with pytest.raises(capi.StrainCallError) as ei:
+            dev.classify([b"ACGTACGTAC", b""], [1, 2])
+        assert ei.value.code == -4 and "query 1 has 0 bases (1..8192 supported)" in str(ei.value)
+        best, winners, words, _ = dev.classify([b"A" * 8192], [1])
+        assert int(best[0]) in (0, 1) and int(words[0]) == 8185 and winners.shape == (1, 100)
+
+
+# ---- named edge cases (taxa_lib holds them with their property checks) --------------------------------------------------------
+
+_ONCE = {}
+
+
+def _once(name, make):
+    """A case or an expected result, built once for the tests that read it."""
+    if name not in _ONCE:
+        _ONCE[name] = make()
+    return _ONCE[name]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _shared_cases_end_with_this_module():
+    yield
+    _ONCE.clear()
+    T.forget_models()
+
+
+@pytest.mark.parametrize("grid_cap", [0, 1])
+def test_table_cells_next_to_a_half_integer(grid_cap):
+    """Cells 1e-9 .. 3e-8 from a half-integer, one rounding down and two up, equal to the exact table; 128 workgroups (or one,
+    128 times) add to one cell."""
+    for mo in _once("near_half", T.near_half_case):
+        with _train(mo, grid_cap, keep_counts=True) as dev:
+            _check_model(dev, mo)
+
+
+@pytest.mark.parametrize("grid_cap", [0, 1])
+def test_word_kernel_lane_seams(grid_cap):
+    """grid_cap 1: one workgroup takes every sequence in turn, the shortest right after the longest."""
+    mo = _once("seam", T.seam_case)
+    with _train(mo, grid_cap, keep_counts=True) as dev:
+        _check_model(dev, mo)
+
+
+def test_training_text_at_an_offset():
+    """sc_taxa_train with seq_off[0] = 5 and 5 bases in front of the text gives the counts and the table of the call from 0."""
+    import ctypes as C
+    from rambl_amd import capi
+    mo = _once("seam", T.seam_case)
+    text = (T.SEAM_JUNK + "".join(mo.seqs)).encode()
+    off = np.array([0] + [len(s) for s in mo.seqs], dtype=np.int64).cumsum() + len(T.SEAM_JUNK)
+    assert off[0] == 5 and text[:off[1] - 5] != mo.seqs[0].encode() and text[off[0]:off[1]] == mo.seqs[0].encode()
+    gi = np.ascontiguousarray(mo.genus, dtype=np.int32)
+    dev = capi.TaxaModel.__new__(capi.TaxaModel)
+    dev.n_genera, dev._h, dev.stats = mo.G, C.c_void_p(), capi.ScTaxaStats()
+    rc = capi.lib().sc_taxa_train(0, text, off.ctypes.data_as(C.POINTER(C.c_long)), mo.N, gi.ctypes.data_as(C.POINTER(C.c_int)), mo.G, 0, 1,
+                                  C.byref(dev._h), C.byref(dev.stats))
+    assert rc == 0, capi.lib().sc_taxa_error().decode()
+    with dev:
+        _check_model(dev, mo)
+
+
+@pytest.mark.parametrize("G", [1, 2, 2 * T.CHUNK, 2 * T.CHUNK + 1])
+def test_winners_by_genera_count(G):
+    """One and two live lanes in a chunk, exactly two chunks, a third with one live lane."""
+    mo = T.shared_model(G)
+    qs = T.genera_queries(mo)
+    exp = _expected(mo, qs, SEED)
+    names = [n for n, _ in qs]
+    assert exp[names.index("last")][0] == G - 1 and exp[names.index("middle")][0] == G // 2 and exp[names.index("w0")] == (-1, [-1] * 100, 0)
+    with _train(mo) as dev:
+        for grid_cap in (0, 1):
+            assert _classify(dev, qs, SEED, grid_cap=grid_cap) == exp, grid_cap
+
+
+def test_ties_and_winners_over_four_chunks():
+    G = 3 * T.CHUNK + 1
+    mo = T.shared_model(G, T.TWINS3)
+    qs = T.genera_queries(mo, T.TWINS3)
+    exp = _expected(mo, qs, SEED)
+    res = dict((n, r) for (n, _), r in zip(qs, exp))
+    for a in (3, 5, 80, 130):                                   # chunks 0 = 1 = 2; 0 = 2; 1 = 2; inside chunk 2: the lowest genus, in every trial
+        assert res["tie%d" % a][0] == a and set(res["tie%d" % a][1]) == {a}
+    assert res["middle"][0] == G // 2 and (G // 2) // T.CHUNK == 1 and res["last"][0] == G - 1 == 192 and res["first"][0] == 0
+    with _train(mo) as dev:
+        for grid_cap in (0, 1):
+            assert _classify(dev, qs, SEED, grid_cap=grid_cap) == exp, grid_cap
+
+
+def test_query_lengths_in_one_call():
+    """W = 2 .. 8 and around 256 and 1 024 words, the W = 0 queries and the longest query in one call; the decisive queries
+    lose their winner with a single word."""
+    mo = T.shared_model(70, T.TWINS)
+    qs = _once("lengths", lambda: T.lengths_case(mo))
+    exp = _once("lengths_exp", lambda: _expected(mo, qs, SEED))
+    for (name, _), (best, winners, W) in zip(qs, exp):
+        if name[0] == "d":
+            assert W == int(name[1:].split("_")[0]) and best > 0 and best in winners and set(winners) <= {0, best}, name
+    assert [r[2] for (n, _), r in zip(qs, exp) if n in ("w0_short", "long", "w0_n")] == [0, 8185, 0]
+    # grid_cap 1: one workgroup makes every (query, chunk) trip, query after query within a chunk, so in both chunks the 2 words
+    # of "d2_1" are staged right after the 8 185 of "long"
+    n_chunks = (mo.G + T.CHUNK - 1) // T.CHUNK
+    names = [n for n, _ in qs]
+    assert n_chunks == 2 and n_chunks * len(qs) == 66 and names[names.index("long") + 1] == "d2_1"
+    assert exp[names.index("long")][2] == 8185 and exp[names.index("d2_1")][2] == 2
+    with _train(mo) as dev:
+        for grid_cap in (0, 1):
+            got = _classify(dev, qs, SEED, grid_cap=grid_cap)
+            for (name, _), g, e in zip(qs, got, exp):
+                assert g == e, (name, grid_cap)
+
+
+def test_trial_counts_around_the_wavefronts():
+    """2 .. 8 trials: wavefronts without a trial, and with one more than their neighbour."""
+    mo = T.shared_model(70, T.TWINS)
+    qs = T.score_queries(mo, T.TWINS)
+    with _train(mo) as dev:
+        for n_trials in (2, 3, 4, 5, 7, 8):
+            exp = _expected(mo, qs, SEED, n_trials)
+            assert all(len(r[1]) == n_trials for r in exp)
+            for grid_cap in (0, 1):
+                assert _classify(dev, qs, SEED, n_trials, grid_cap) == exp, (n_trials, grid_cap)
+
+
+def test_most_trials_and_most_draws():
+    """1 024 trials of 5, 6 and 1 023 draws: the largest t * 65536 + j + 1."""
+    mo = T.shared_model(70, T.TWINS)
+    qs = T.max_trials_queries(mo)
+    exp = _expected(mo, qs, SEED, 1024)
+    assert [r[2] for r in exp] == [1, 48, 8185] and len(set(exp[2][1])) > 1 and len(set(exp[2][1][-4:] + exp[1][1][-4:])) > 1
+    with _train(mo) as dev:
+        for grid_cap in (0, 1):
+            got = _classify(dev, qs, SEED, 1024, grid_cap)
+            for (name, _), g, e in zip(qs, got, exp):
+                assert g == e, (name, grid_cap)
+
+
+def test_keys_and_seeds_at_the_ends_of_64_bits():
+    mo = T.shared_model(70, T.TWINS)
+    qs = T.score_queries(mo, T.TWINS)
+    exp = _once("keys", lambda: T.keys_case(mo, qs))
+    with _train(mo) as dev:
+        for name, key, seed in T.KEY_SEEDS:
+            keys = [T.fnv1a64(n.encode()) if key is None else key for n, _ in qs]
+            for grid_cap in (0, 1):
+                best, winners, words, _ = dev.classify([s.encode() for _, s in qs], keys, seed, 100, grid_cap)
+                got = [(int(best[i]), [int(w) for w in winners[i]], int(words[i])) for i in range(len(qs))]
+                assert got == exp[name], (name, grid_cap)
 
 
 def test_classify_command_line(tmp_path):

@@ -11,6 +11,43 @@ def test_every_named_case_reaches_its_edge():
     assert T.check_cases_on_the_cpu()
 
 
+def test_exact_table_by_hand_and_its_error_bound():
+    import numpy as np
+    # N = 1: P_w = 0.25 for a word nobody holds, and with M = 0 the cell is log2(0.25) * 1024 = -2048 exactly, half a unit from
+    # either half-integer (M = 1: -3072); the word one sequence holds has P_w = 0.75: log2(0.75) * 1024 = -424.99839926...
+    # with m = 0, M = 0, and with n = m = M = 1 p = (1 + 0.75) / 2 = 0.875, log2(0.875) * 1024 = -197.26855981...
+    n, m, M = np.array([0, 1]), np.array([[0, 0], [0, 1]]), np.array([0, 1])
+    q, d = T.table_exact(n, m, M, 1)
+    assert q.tolist() == [[-2048, -3072], [-425, -197]] and d[0, 0] == 0.5 and d[0, 1] == 0.5
+    assert abs(d[1, 1] - (197.5 - 197.26855981301338)) < 1e-12 and abs(d[1, 0] - (0.5 - (425 - 424.99839926153606))) < 1e-12
+    assert (T.table(n, m, M, 1) == q).all()
+    # the bound: 4.9e-13 from the roundings of p, the rest grows with |x|; at the contract's largest cell it is under 3e-11
+    assert 4.9e-13 < T.table_error_bound(0.0) < 5.0e-13 and 2.8e-11 < T.table_error_bound(50 * 1024) < 3e-11
+    # the near-half-integer tuples keep their recorded distances, each 100 E away and nearer than 1e-7
+    dist = [float(mo.dist[T.word_of("ACGTTGCA"), 0]) for mo in T.near_half_case()]
+    for got, want in zip(dist, (2.7462e-8, 9.7189e-9, 1.1418e-9)):
+        assert abs(got / want - 1.0) < 1e-3 and got > 100 * T.table_error_bound(900.0)
+    # a cell inside the bound is refused: the cap is asserted from the reference alone
+    near = T.table_exact
+    try:
+        T.table_exact = lambda *a: (np.array([[-692]]), np.array([[1e-13]]))
+        with pytest.raises(AssertionError):
+            T.exact_checked(n, m, M, 1)
+    finally:
+        T.table_exact = near
+
+
+def test_draw_at_the_limits_equals_the_restatement():
+    """The last draw of the last trial, and seed ^ key at 0, at all ones and one below: the 64-bit sum wraps."""
+    from rambl_amd import capi
+    for seed, key in ((0, 0), (T.MASK, 0), (0, T.MASK), (T.MASK, T.MASK), (T.MASK, 1), (977, 977)):
+        for t, j in ((0, 0), (1, 0), (1023, 1022), (1023, 0), (512, 5)):
+            for W in (1, 2, 48, 8185):
+                got = capi.taxa_draw(seed, key, t, j, W)
+                assert got == T.draw(seed, key, t, j, W) and 0 <= got < W
+    assert 1023 * 65536 + 1022 + 1 < 2 ** 32
+
+
 def test_draw_equals_the_restatement():
     from rambl_amd import capi
     for W in (1, 7, 8, 40, 8185):
