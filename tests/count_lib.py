@@ -81,6 +81,7 @@ class CountCase:
 
 
 _REFERENCE = {}
+_LOOSE = {}
 
 
 def hits_in_parts(exe, genes, segs, thresholds, jobs=8):
@@ -102,8 +103,26 @@ def reference(case, exe):
         th = case.thresholds
         loose = hits_in_parts(exe, case.genes, case.segs, (0.0,) + tuple(th[1:]))
         hits = [h for h in loose if 100.0 * h[4] / h[5] >= th[0]]
+        _LOOSE[case.name] = loose
         _REFERENCE[case.name] = (PL.rows_of(hits, case.ids, lens, case.names), PL.rows_of(loose, case.ids, lens, case.names))
     return _REFERENCE[case.name]
+
+
+def loose_hits(case, exe=None):
+    """The restatement's own hits of a case at -I 0 (profile_lib.run_hits_check's tuples: strand and doubled score, which the
+    rows do not carry), kept by reference(); without exe: for a case's check, which runs after reference()."""
+    if exe is not None:
+        reference(case, exe)
+    return _LOOSE[case.name]
+
+
+def groups_of(all_rows, min_identity=95.0, max_evalue=1e-10):
+    """{read: its rows at -I 0 with E6 <= T grouped by E6, smallest first}: the groups lazy_rule walks, in its order."""
+    reads = {}
+    for r in all_rows:
+        if float(r[8]) <= max_evalue:
+            reads.setdefault(read_of(r[0]), {}).setdefault(float(r[8]), []).append(r)
+    return {read: [groups[e6] for e6 in sorted(groups)] for read, groups in reads.items()}
 
 
 def check_rules(case, exe):
