@@ -4,15 +4,18 @@
 // /root/reference/StrainCall/PartialOrderGraph.cpp:67-265 (thread reads by CIGAR,
 // canonise insertions/deletions, forward/backward merge, path collapse, level
 // numbering) with index-based storage, tombstoned deletion and linear-time pool
-// intersections, then flattens it into the level-major arrays the HIP clustering
-// kernels consume (sc_graph_kernels.hip).  The insertion MSA (row a7) is delegated to
-// the device through `MsaFn`.
+// intersections (sc_graph.cpp), then flattens it into the level-major arrays the HIP
+// clustering kernels consume (sc_flatten.cpp; the kernels: sc_graph_kernels.hip).
+// The insertion MSA (row a7) is delegated to the device through `MsaFn`.
 #pragma once
+#include <atomic>
 #include <cstdint>
 #include <functional>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
+#include "sc_std_sort.hpp"
 
 namespace sc {
 
@@ -116,21 +119,41 @@ private:
     void path_collapse();
     void node_level();
     void finalize_ids();
+    struct Threading;          // the steps of thread_reads and their state (sc_graph.cpp)
     void thread_reads(const std::string& G, const std::vector<AlignedRead>& R, const ThreadFn& thread);
 };
 
-// libstdc++ std::sort permutation (the reference depends on its tie order at
-// PartialOrderGraph.cpp:466, NonparametricClustering.cpp:647,675, StrainCall.cpp:1027).
-// less(a,b) compares element identities a,b (values stored in idx).
-void std_sort_perm(std::vector<int>& idx, const std::function<bool(int, int)>& less);
-
 // ---------------------------------------------------------------------------
-// Level-major flattening for the device.
 // Host threads the construction of ONE region's graph may use for its bulk copies (class pools, flattening): 1 while many
 // regions are in flight (they already fill the rank's CPUs), more for a single deep region (BASELINE configs[3]: 88 M pool
-// entries).  Thread-local: set by the worker that builds the graph.
-void set_graph_threads(int n);
-int graph_threads();
+// entries).  A bulk copy of `min_entries` pool entries or fewer stays on the calling thread.  Thread-local: set by the
+// worker that builds the graph.
+void set_graph_threads(int n, long min_entries = 1L << 22);
+int graph_threads(long entries);       // threads for a bulk copy of that many pool entries
+
+// fn(i, scratch) for i in [0, n), on up to `threads` threads taking indices from a shared counter (the items differ in size
+// by orders of magnitude: a backbone class of 59 000 reads beside a sibling of three); every thread makes a scratch of its
+// own with scratch().  On one thread the items run in order.  Exceptions of a helper end the process as they would on the
+// calling thread.
+template <class S, class F>
+void parallel_items(int n, int threads, const S& scratch, const F& fn) {
+    std::atomic<int> next{0};
+    auto body = [&] {
+        auto s = scratch();
+        for (int i = next.fetch_add(1, std::memory_order_relaxed); i < n; i = next.fetch_add(1, std::memory_order_relaxed)) fn(i, s);
+    };
+    std::vector<std::thread> ts;
+    for (int t = 1; t < threads && n >= 2; t++) ts.emplace_back(body);
+    body();
+    for (auto& t : ts) t.join();
+}
+template <class F>
+void parallel_items(int n, int threads, const F& fn) {
+    parallel_items(n, threads, [] { return 0; }, [&](int i, int&) { fn(i); });
+}
+
+// ---------------------------------------------------------------------------
+// Level-major flattening for the device (sc_flatten.cpp).
 
 struct FlatGraph {
     // symbol table: code 0..5 = A C G T - = ; further codes in order of appearance

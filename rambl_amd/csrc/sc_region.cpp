@@ -1,7 +1,8 @@
 // A region's set-up on its worker: the partial order graph (sc_graph.cpp; the per-base threading of the reads and the
-// insertion MSA run on the device: k_thread_*, k_msa), flattened level-major, uploaded once, every edge support computed
-// on the device (k_edge_support).  Then the level walk (sc_walk.cpp).
+// insertion MSA run on the device: k_thread_*, k_msa), flattened level-major (sc_flatten.cpp), uploaded once, every edge
+// support computed on the device (k_edge_support).  Then the level walk (sc_walk.cpp).
 #include "sc_ctx.hpp"
+#include "sc_phase_timer.hpp"
 
 namespace sc {
 
@@ -60,12 +61,8 @@ int Worker::msa_device(const std::vector<std::string>& seqs, std::vector<std::st
 void Worker::thread_device(const std::string& G, const std::vector<AlignedRead>& R, const std::vector<std::vector<CigarOp>>& cig,
                            ThreadTables& T) {
     const int glen = (int)G.size(), n = (int)R.size();
-#ifdef SC_GRAPH_TIMING
-    double tdp_ = now_ms();
-#define SC_DPHASE(name) do { HIPCHK(hipStreamSynchronize(st)); const double t_ = now_ms(); fprintf(stderr, "      thread_device %-12s %.2f ms\n", name, t_ - tdp_); tdp_ = t_; } while (0)
-#else
-#define SC_DPHASE(name) do {} while (0)
-#endif
+    PhaseTimer tp("      thread_device ", 12);                    // an experiment build waits for the stream at every phase
+    auto dphase = [&](const char* name) { if (PhaseTimer::on) { HIPCHK(hipStreamSynchronize(st)); tp.phase(name); } };
     // symbol table of the READS: A C G T first, then every other byte that occurs in a read, in byte order.  A base of the
     // gene that no read carries (an IUPAC code of a 16S reference) keeps the code 0xFF: no read base equals it, so every
     // read base aligned there lands in a sibling class, as `G[i]==r[j]` decides in the reference (PartialOrderGraph.cpp:133)
@@ -88,7 +85,7 @@ void Worker::thread_device(const std::string& G, const std::vector<AlignedRead>&
         for (const CigarOp& c : cig[r]) { cig_op.push_back(c.op); cig_len.push_back(c.len); if (c.op == 'M') m_bases += c.len; }
         cig_off[r + 1] = (int)cig_op.size();
     }
-    SC_DPHASE("pack");
+    dphase("pack");
     const int ncls = glen * 8;
     ThreadDev d{};
     d.glen = glen; d.n_reads = n;
@@ -118,9 +115,9 @@ void Worker::thread_device(const std::string& G, const std::vector<AlignedRead>&
     HIPCHK(hipMemsetAsync(d.off, 0, sizeof(int) * ((size_t)ncls * 2 + 3), st));           // off, cursor, err, the count of big classes
     d.pool = (int*)t_pool.ensure(sizeof(int) * (size_t)std::max<long>(m_bases, 1));
     int* pool_sorted = (int*)t_pool2.ensure(sizeof(int) * (size_t)std::max<long>(m_bases, 1));
-    SC_DPHASE("uploads");
+    dphase("uploads");
     launch_thread(st, d, pool_sorted);
-    SC_DPHASE("kernels");
+    dphase("kernels");
     T.count.resize(ncls); T.minrid.resize(ncls); T.smin.resize(ncls); T.emin.resize(ncls);
     T.tmin.resize((size_t)ncls * 8); T.off.resize((size_t)ncls + 1); T.pool.resize((size_t)m_bases);
     int err = 0;
@@ -136,8 +133,7 @@ void Worker::thread_device(const std::string& G, const std::vector<AlignedRead>&
     sync_stream();
     stage->land();
     if (ctx->plan.opt.sync_log) fprintf(stderr, "sync thread_device %.3f ms\n", now_ms() - t_sync0);
-    SC_DPHASE("downloads");
-#undef SC_DPHASE
+    dphase("downloads");
     if (err) throw ScError(SC_ERR_ARG, "a read runs outside the window or past its own bases");
     const int INF = 0x7fffffff;
     auto fix = [&](std::vector<int>& v) { for (int& x : v) if (x == 0x7f7f7f7f) x = INF; };

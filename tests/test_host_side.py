@@ -63,8 +63,8 @@ def test_ingest_matches_oracle(seed, tmp_path, oracle_bin):
 def graph_check_bin(oracle_bin, tmp_path_factory):
     out = str(tmp_path_factory.mktemp("native") / "graph_host_check")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", out, os.path.join(ROOT, "tests", "native", "graph_host_check.cpp"),
-                           os.path.join(ROOT, "rambl_amd", "csrc", "sc_graph.cpp"), "-L" + os.path.join(ROOT, "oracle"),
-                           "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle")])
+                           *[os.path.join(ROOT, "rambl_amd", "csrc", f) for f in ("sc_graph.cpp", "sc_flatten.cpp", "sc_std_sort.cpp")],
+                           "-L" + os.path.join(ROOT, "oracle"), "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread"])
     return out
 
 
@@ -85,6 +85,78 @@ def test_host_graph_matches_oracle(seed, tmp_path, oracle_bin, graph_check_bin):
             got += p.stdout.decode()
         i += 1
     assert got == exp_g
+
+
+# seeds 0-15 of make_case (reads with I and D, no symbol beyond A C G T) and a hand-made dump of 20 reads with one
+# insertion, one deletion up to "$" and the symbols N and R: the smallest shape at which the label merge order, K and
+# code_N can go wrong
+FLAT_CASES = list(range(0, 16)) + ["hand"]
+
+
+def _flat_digests(case, d, graph_check_bin, threads, min_entries):
+    """{field: digest} of every region of the case that has reads, from `graph_host_check --flat-digest`."""
+    if case == "hand":
+        paths = [os.path.join(ROOT, "tests", "golden", "flat_hand_dump.txt")]
+    else:
+        base = os.path.join(d, "dump")
+        T.run_oracle(T.make_case(case, d), d, graph=True, dump_reads=base)
+        paths = []
+        i = 0
+        while os.path.exists("%s.%d" % (base, i)):
+            if len(open("%s.%d" % (base, i)).read().splitlines()) > 2:
+                paths.append("%s.%d" % (base, i))
+            i += 1
+    p = subprocess.run([graph_check_bin, "--flat-digest", str(threads), str(min_entries)] + paths, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode == 0, p.stderr.decode()
+    regions = []
+    for line in p.stdout.decode().splitlines():
+        if line.startswith("== "):
+            regions.append({})
+        else:
+            k, v = line.split()
+            regions[-1][k] = v
+    assert len(regions) == len(paths) and all(len(r) == 30 for r in regions)
+    return regions
+
+
+@pytest.fixture(scope="session")
+def flat_digests_serial(oracle_bin, graph_check_bin, tmp_path_factory):
+    """The one-thread digests of every case, computed once for the two tests below."""
+    return {case: _flat_digests(case, str(tmp_path_factory.mktemp("flat")), graph_check_bin, 1, 1 << 22) for case in FLAT_CASES}
+
+
+@pytest.mark.parametrize("case", FLAT_CASES)
+def test_flatten_threaded_equals_serial(case, tmp_path, graph_check_bin, flat_digests_serial):
+    """Every FlatGraph array and every PoGraph pool at 4 threads with the threshold at 0 (the class pools, the pool copy,
+    the label scan and the level fill all on helper threads) equals the one-thread result."""
+    assert _flat_digests(case, str(tmp_path), graph_check_bin, 4, 0) == flat_digests_serial[case]
+
+
+@pytest.mark.parametrize("case", FLAT_CASES)
+def test_flatten_serial_equals_recorded(case, flat_digests_serial):
+    """The one-thread digests equal those recorded from sc_graph.cpp as it stood before flatten and thread_reads were
+    split (tests/golden/flat_digests.json; recorded twice, every case deterministic)."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "flat_digests.json")))
+    assert flat_digests_serial[case] == want[str(case)]
+
+
+def _sort_cases():
+    """Key sets full of ties at the sizes around libstdc++'s thresholds (16: insertion sort; 2 log2 n: heap fallback)."""
+    rng = random.Random(3)
+    cases = []
+    for _ in range(300):
+        n = rng.choice([1, 2, 5, 16, 17, 18, 33, 80, 81, 200, 1000])
+        cases.append([float(rng.randint(0, max(1, n // rng.choice([1, 2, 8])))) for _ in range(n)])
+    return cases
+
+
+def test_product_sort_port_matches_libstdcxx(graph_check_bin):
+    """sc::std_sort_perm (sc_std_sort.cpp) and the real std::sort in one binary, on the key sets of the test below."""
+    text = "\n".join("%d %s" % (len(k), " ".join(map(repr, k))) for k in _sort_cases())
+    p = subprocess.run([graph_check_bin, "--sort-check"], input=text.encode(), stdout=subprocess.PIPE)
+    assert p.returncode == 0, p.stdout.decode()
+    assert p.stdout.decode().strip() == "300 cases equal"
 
 
 def test_sort_port_matches_libstdcxx(tmp_path, oracle_bin):
