@@ -2,6 +2,9 @@
 
 There is no CPU fallback: importing this module fails loudly when the HIP
 library has not been built, and `Context()` fails when no gfx950 device exists.
+
+The ABI is stated once, in ENTRIES (one row per function of the header) and the Structure mirrors above it;
+tests/test_capi_table.py holds both against the header, declaration by declaration and member by member.
 """
 import ctypes as C
 import os
@@ -10,8 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libstraincall_hip.so")
 
 SC_OK = 0
-ERRORS = {-1: "SC_ERR_NO_DEVICE", -2: "SC_ERR_HIP", -3: "SC_ERR_ARG", -4: "SC_ERR_UNSUPPORTED",
-          -5: "SC_ERR_CAPACITY", -6: "SC_ERR_INTERNAL"}
+ERRORS = dict(zip(range(-1, -7, -1), ("SC_ERR_NO_DEVICE", "SC_ERR_HIP", "SC_ERR_ARG", "SC_ERR_UNSUPPORTED", "SC_ERR_CAPACITY", "SC_ERR_INTERNAL")))
+SC_ERR_NO_DEVICE, SC_ERR_HIP, SC_ERR_ARG, SC_ERR_UNSUPPORTED, SC_ERR_CAPACITY, SC_ERR_INTERNAL = ERRORS
 
 
 class ScParams(C.Structure):
@@ -20,62 +23,54 @@ class ScParams(C.Structure):
                 ("graph_only", C.c_int), ("want_trace", C.c_int), ("want_timing", C.c_int), ("want_graph", C.c_int)]
 
 
-class ScStats(C.Structure):
+class Stats(C.Structure):
+    """The statistics structs of the header; the derived mirrors below state the header's flat member lists by concatenation."""
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if issubclass(t, C.Array) else getattr(self, k)) for k, t in self._fields_}
+
+
+class ScStats(Stats):
     _fields_ = [("graph_ms", C.c_double), ("cluster_ms", C.c_double), ("sampler_kernel_ms", C.c_double),
                 ("sampler_launches", C.c_long), ("sampler_read_copies", C.c_long), ("level_launches", C.c_long), ("draws", C.c_long),
                 ("slow_draws", C.c_long), ("exact_draws", C.c_long), ("sampler_strains", C.c_long), ("chain_passes", C.c_long), ("chain_cycles", C.c_long), ("chain_wall_ticks", C.c_long), ("level_kernel_ticks", C.c_long), ("sampler_level_ticks", C.c_long), ("xcd_levels", C.c_long * 8), ("msa_calls", C.c_long), ("n_nodes", C.c_int), ("n_levels", C.c_int),
                 ("n_unique_reads", C.c_int), ("n_read_copies", C.c_long), ("setup_ms", C.c_double), ("queue_ms", C.c_double), ("place_ms", C.c_double), ("mailbox_ms", C.c_double), ("host_us", C.c_double * 3), ("wake_us", C.c_double * 2), ("kind_levels", C.c_long * 17)]
 
-    def as_dict(self):
-        return {k: (list(getattr(self, k)) if k in ("xcd_levels", "kind_levels", "host_us", "wake_us") else getattr(self, k)) for k, _ in self._fields_}
+
+class ScDepthStats(Stats):
+    _fields_ = [("cells", C.c_long), ("runs", C.c_long), ("extract_ms", C.c_double), ("prepare_ms", C.c_double),
+                ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
-class ScAlignStats(C.Structure):
+class ScAlignStats(Stats):
     _fields_ = [("upload_ms", C.c_double), ("score_ms", C.c_double), ("trace_ms", C.c_double), ("total_ms", C.c_double),
                 ("score_cells", C.c_long), ("trace_cells", C.c_long), ("n_traced", C.c_long)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class ScProfileStats(C.Structure):
+class ScProfileStats(Stats):
     _fields_ = [("upload_ms", C.c_double), ("score_ms", C.c_double), ("trace_ms", C.c_double), ("total_ms", C.c_double),
                 ("score_cells", C.c_long), ("trace_cells", C.c_long), ("n_tiles", C.c_long), ("n_candidates", C.c_long),
                 ("n_traced", C.c_long), ("n_hits", C.c_long)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class ScProfileSeedStats(C.Structure):
+class ScProfileSeedStats(Stats):
     _fields_ = ScProfileStats._fields_ + [("seed_k", C.c_int), ("n_gene_kmers", C.c_long), ("n_pairs", C.c_long),
                                           ("index_ms", C.c_double), ("lookup_ms", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class ScProfileCountStats(C.Structure):
+class ScProfileCountStats(Stats):
     _fields_ = ScProfileSeedStats._fields_ + [("n_rounds", C.c_int), ("n_stretches", C.c_int), ("n_reads_counted", C.c_long),
                                               ("select_ms", C.c_double), ("count_ms", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class ScProfileCohortStats(C.Structure):
+class ScProfileCohortStats(Stats):
+    """The header nests a sc_profile_count_stats as `counts`; the mirror holds its members flat, under their own names."""
     _fields_ = ScProfileCountStats._fields_ + [("n_samples", C.c_int), ("n_index_builds", C.c_int), ("n_allocs", C.c_long)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class ScTaxaStats(C.Structure):
+class ScTaxaStats(Stats):
     _fields_ = [("upload_ms", C.c_double), ("words_ms", C.c_double), ("table_ms", C.c_double), ("score_ms", C.c_double), ("total_ms", C.c_double),
                 ("n_seqs", C.c_long), ("n_words", C.c_long), ("n_genera", C.c_long), ("table_bytes", C.c_long)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class StrainCallError(RuntimeError):
@@ -84,137 +79,81 @@ class StrainCallError(RuntimeError):
         self.code = code
 
 
+# ---- the prototype table: (name, return type, argument types) of every function the header declares, in its order
+
+_i, _l, _d, _u64, _s, _vp = C.c_int, C.c_long, C.c_double, C.c_ulonglong, C.c_char_p, C.c_void_p      # _vp: a pointer to one of the opaque structs
+_ip, _lp, _dp, _up, _bp, _u64p = (C.POINTER(t) for t in (C.c_int, C.c_long, C.c_double, C.c_uint, C.c_ubyte, C.c_ulonglong))
+_vpp, _sp, _ipp = C.POINTER(_vp), C.POINTER(_s), C.POINTER(_ip)
+_HITS = [_i, _s, _lp, _i, _s, _lp, _i, _d, _d, _d, _d, _ip, _ip, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _l, _lp]      # sc_profile_hits*, up to the statistics
+_INTERVALS = [_ip, _ip, _ip, _lp, _ip, _i, _ip, C.POINTER(ScDepthStats)]                                                     # sc_depth_scan*, from iv_ref on
+
+ENTRIES = [
+    ("sc_ctx_create", _i, [_i, _i, _vpp]),
+    ("sc_ctx_destroy", None, [_vp]),
+    ("sc_last_error", _s, [_vp]),
+    ("sc_roi_error", _s, [_vp, _i]),
+    ("sc_host_bind", _i, [_i]),
+    ("sc_host_plan", _i, [_i, _i, _d, _ip]),
+    ("sc_roi_submit", _i, [_vp, _s, _i, _ip, _s, _ip, _s, _ip, _ip, _ip, _ip, _i, C.POINTER(ScParams), _ip]),
+    ("sc_roi_wait", _i, [_vp, _i]),
+    ("sc_roi_result", _i, [_vp, _i, _s, _l, _ip, _dp, _i, _ip]),
+    ("sc_roi_graph_dump", _i, [_vp, _i, _s, _l, _lp]),
+    ("sc_roi_trace", _i, [_vp, _i, _s, _l, _lp]),
+    ("sc_roi_stats", _i, [_vp, _i, C.POINTER(ScStats)]),
+    ("sc_roi_release", _i, [_vp, _i]),
+    ("sc_msa_align", _i, [_vp, _s, _ip, _i, _s, _l, _ip]),
+    ("sc_roi_edge_support", _i, [_vp, _i, _ip, _i, _ip]),
+    ("sc_roi_thread_tables", _i, [_vp, _i, _ip, _ip, _i, _ip, _l, _s, _ip, _lp]),
+    ("sc_roi_thread_edges", _i, [_vp, _i, _ip, _ip, _ip, _i, _ip]),
+    ("sc_edge_support_tables", _i, [_vp, _i, _ip, _ip, _ip, _bp, _i, _ip, _ip, _i, _ip]),
+    ("sc_sample_level", _i, [_vp, _i, _dp, _i, _dp, _bp, _i, _i, _ip, _ip, _ip, _ip, _ip, _i, _dp, _i, _up, _up, _lp]),
+    ("sc_aln_open", _i, [_s, _vpp]),
+    ("sc_aln_open_filtered", _i, [_s, _sp, _i, _vpp]),
+    ("sc_aln_close", None, [_vp]),
+    ("sc_aln_error", _s, [_vp]),
+    ("sc_aln_records", _l, [_vp]),
+    ("sc_aln_ref_stats", _i, [_vp, _s, _lp, _lp]),
+    ("sc_aln_walk", _i, [_vp, _l, _l, _s, _l, _lp, _lp]),
+    ("sc_aln_pileup_flags", _i, [_vp, _s, _i, _i, _i, _bp, _bp, _bp]),
+    ("sc_aln_load_reads", _i, [_vp, _s, _i, _i, _i, _i, _i, _i, _vpp]),
+    ("sc_reads_get", _i, [_vp, _ip, _ipp, _sp, _ipp, _sp, _ipp, _ipp, _ipp, _ipp, _lp, _ip]),
+    ("sc_reads_free", None, [_vp]),
+    ("sc_depth_scan", _i, [_i, _vpp, _i, _sp, _ip, _i, _i] + _INTERVALS),
+    ("sc_depth_scan_runs", _i, [_i, _ip, _i, _ip, _ip, _ip, _l, _i] + _INTERVALS),
+    ("sc_align_reads", _i, [_i, _s, _lp, _i, _s, _s, _lp, _i, _ip, _ip, _ip, _ip, _ip, _ip, _up, _i, _ip, C.POINTER(ScAlignStats)]),
+    ("sc_align_error", _s, []),
+    ("sc_profile_hits", _i, _HITS + [C.POINTER(ScProfileStats)]),
+    ("sc_profile_error", _s, []),
+    ("sc_profile_hits_seeded", _i, _HITS + [C.POINTER(ScProfileSeedStats)]),
+    ("sc_profile_seed_length", _i, [_ip, _i, _l, _d, _d, _d, _d, _ip]),
+    ("sc_profile_counts", _i, [_i, _s, _lp, _i, _s, _lp, _i, _ip, _i, _d, _d, _d, _d, _i, _l, _ip, _ip, _ip, _lp, _l, _lp,
+                               C.POINTER(ScProfileCountStats)]),
+    ("sc_profile_index_create", _i, [_i, _s, _lp, _i, _vpp]),
+    ("sc_profile_index_info", _i, [_vp, _ip, _lp, _ip, _ip]),
+    ("sc_profile_index_counts", _i, [_vp, _s, _lp, _i, _ip, _i, _ip, _i, _d, _d, _d, _d, _i, _l, _ip, _ip, _ip, _ip, _lp, _l, _lp,
+                                     C.POINTER(ScProfileCohortStats)]),
+    ("sc_profile_index_free", None, [_vp]),
+    ("sc_profile_evalue6", _d, [_i, _l, _i, _d, _d]),
+    ("sc_taxa_train", _i, [_i, _s, _lp, _i, _ip, _i, _i, _i, _vpp, C.POINTER(ScTaxaStats)]),
+    ("sc_taxa_classify", _i, [_vp, _s, _lp, _i, _u64p, _u64, _i, _i, _ip, _ip, _ip, C.POINTER(ScTaxaStats)]),
+    ("sc_taxa_model_counts", _i, [_vp, _i, _up, _up]),
+    ("sc_taxa_model_table", _i, [_vp, _i, _ip]),
+    ("sc_taxa_free", None, [_vp]),
+    ("sc_taxa_error", _s, []),
+    ("sc_taxa_draw", _l, [_u64, _u64, _i, _i, _i]),
+]
+EXPORTS = [name for name, _, _ in ENTRIES]
+
+
 def load_library():
     if not os.path.exists(LIB_PATH):
         raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950). There is no CPU fallback for the StrainCall path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    vp, ip, cp = C.c_void_p, C.POINTER(C.c_int), C.c_char_p
-    lib.sc_ctx_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
-    lib.sc_ctx_destroy.argtypes = [vp]
-    lib.sc_ctx_destroy.restype = None
-    lib.sc_last_error.argtypes = [vp]
-    lib.sc_last_error.restype = cp
-    lib.sc_roi_error.argtypes = [vp, C.c_int]
-    lib.sc_roi_error.restype = cp
-    lib.sc_host_plan.argtypes = [C.c_int, C.c_int, C.c_double, ip]
-    lib.sc_host_plan.restype = C.c_int
-    lib.sc_host_bind.argtypes = [C.c_int]
-    lib.sc_host_bind.restype = C.c_int
-    lib.sc_roi_submit.argtypes = [vp, cp, C.c_int, ip, cp, ip, cp, ip, ip, ip, ip, C.c_int, C.POINTER(ScParams), ip]
-    lib.sc_roi_wait.argtypes = [vp, C.c_int]
-    lib.sc_roi_result.argtypes = [vp, C.c_int, C.c_char_p, C.c_long, ip, C.POINTER(C.c_double), C.c_int, ip]
-    lib.sc_roi_graph_dump.argtypes = [vp, C.c_int, C.c_char_p, C.c_long, C.POINTER(C.c_long)]
-    lib.sc_roi_trace.argtypes = [vp, C.c_int, C.c_char_p, C.c_long, C.POINTER(C.c_long)]
-    lib.sc_roi_stats.argtypes = [vp, C.c_int, C.POINTER(ScStats)]
-    lib.sc_roi_release.argtypes = [vp, C.c_int]
-    lib.sc_roi_edge_support.argtypes = [vp, C.c_int, ip, C.c_int, ip]
-    lib.sc_msa_align.argtypes = [vp, cp, ip, C.c_int, C.c_char_p, C.c_long, ip]
-    lib.sc_roi_thread_tables.argtypes = [vp, C.c_int, ip, ip, C.c_int, ip, C.c_long, C.c_char_p, ip, C.POINTER(C.c_long)]
-    lib.sc_roi_thread_edges.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, ip]
-    lib.sc_edge_support_tables.argtypes = [vp, C.c_int, ip, ip, ip, C.POINTER(C.c_ubyte), C.c_int, ip, ip, C.c_int, ip]
-    dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint)
-    lib.sc_sample_level.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.POINTER(C.c_ubyte), C.c_int, C.c_int, ip, ip, ip, ip, ip,
-                                    C.c_int, dp, C.c_int, up, up, C.POINTER(C.c_long)]
-    pi, pc, pu = C.POINTER(ip), C.POINTER(C.c_char_p), C.POINTER(C.c_ubyte)
-    lib.sc_aln_open.argtypes = [cp, C.POINTER(vp)]
-    lib.sc_aln_open_filtered.argtypes = [cp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(vp)]
-    lib.sc_aln_open_filtered.restype = C.c_int
-    lib.sc_aln_close.argtypes = [vp]
-    lib.sc_aln_close.restype = None
-    lib.sc_aln_error.argtypes = [vp]
-    lib.sc_aln_error.restype = cp
-    lib.sc_aln_records.argtypes = [vp]
-    lib.sc_aln_records.restype = C.c_long
-    lib.sc_aln_ref_stats.argtypes = [vp, cp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
-    lib.sc_aln_ref_stats.restype = C.c_int
-    lib.sc_aln_pileup_flags.argtypes = [vp, cp, C.c_int, C.c_int, C.c_int, pu, pu, pu]
-    lib.sc_aln_load_reads.argtypes = [vp, cp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
-    lib.sc_reads_get.argtypes = [vp, ip, pi, pc, pi, pc, pi, pi, pi, pi, C.POINTER(C.c_long), ip]
-    lib.sc_reads_free.argtypes = [vp]
-    lib.sc_reads_free.restype = None
-    lib.sc_aln_walk.argtypes = [vp, C.c_long, C.c_long, C.c_char_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]
-    lp = C.POINTER(C.c_long)
-    lib.sc_align_reads.argtypes = [C.c_int, cp, lp, C.c_int, cp, cp, lp, C.c_int, ip, ip, ip, ip, ip, ip, up, C.c_int, ip,
-                                   C.POINTER(ScAlignStats)]
-    lib.sc_align_error.argtypes = []
-    lib.sc_align_error.restype = cp
-    lib.sc_profile_hits.argtypes = [C.c_int, cp, lp, C.c_int, cp, lp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, ip, ip, ip,
-                                    dp, ip, ip, ip, ip, ip, ip, dp, C.c_long, lp, C.POINTER(ScProfileStats)]
-    lib.sc_profile_error.argtypes = []
-    lib.sc_profile_error.restype = cp
-    lib.sc_profile_hits_seeded.argtypes = lib.sc_profile_hits.argtypes[:-1] + [C.POINTER(ScProfileSeedStats)]
-    lib.sc_profile_seed_length.argtypes = [ip, C.c_int, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, ip]
-    lib.sc_profile_counts.argtypes = [C.c_int, cp, lp, C.c_int, cp, lp, C.c_int, ip, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
-                                      C.c_int, C.c_long, ip, ip, ip, lp, C.c_long, lp, C.POINTER(ScProfileCountStats)]
-    lib.sc_profile_index_create.argtypes = [C.c_int, cp, lp, C.c_int, C.POINTER(vp)]
-    lib.sc_profile_index_info.argtypes = [vp, ip, lp, ip, ip]
-    lib.sc_profile_index_counts.argtypes = [vp, cp, lp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
-                                            C.c_int, C.c_long, ip, ip, ip, ip, lp, C.c_long, lp, C.POINTER(ScProfileCohortStats)]
-    lib.sc_profile_index_free.argtypes = [vp]
-    lib.sc_profile_index_free.restype = None
-    lib.sc_profile_evalue6.argtypes = [C.c_int, C.c_long, C.c_int, C.c_double, C.c_double]
-    lib.sc_profile_evalue6.restype = C.c_double
-    u64, u64p = C.c_ulonglong, C.POINTER(C.c_ulonglong)
-    lib.sc_taxa_train.argtypes = [C.c_int, cp, lp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(ScTaxaStats)]
-    lib.sc_taxa_classify.argtypes = [vp, cp, lp, C.c_int, u64p, u64, C.c_int, C.c_int, ip, ip, ip, C.POINTER(ScTaxaStats)]
-    lib.sc_taxa_model_counts.argtypes = [vp, C.c_int, up, up]
-    lib.sc_taxa_model_table.argtypes = [vp, C.c_int, ip]
-    lib.sc_taxa_free.argtypes = [vp]
-    lib.sc_taxa_free.restype = None
-    lib.sc_taxa_error.argtypes = []
-    lib.sc_taxa_error.restype = cp
-    lib.sc_taxa_draw.argtypes = [u64, u64, C.c_int, C.c_int, C.c_int]
-    lib.sc_taxa_draw.restype = C.c_long
-    for f in ("sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table"):
-        getattr(lib, f).restype = C.c_int
-    for f in ("sc_aln_open", "sc_aln_pileup_flags", "sc_aln_load_reads", "sc_reads_get", "sc_aln_walk", "sc_align_reads", "sc_profile_hits",
-              "sc_profile_hits_seeded", "sc_profile_seed_length", "sc_profile_counts", "sc_profile_index_create", "sc_profile_index_info",
-              "sc_profile_index_counts"):
-        getattr(lib, f).restype = C.c_int
-    for f in ("sc_ctx_create", "sc_roi_submit", "sc_roi_wait", "sc_roi_result", "sc_roi_graph_dump", "sc_roi_trace",
-              "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align", "sc_roi_thread_tables", "sc_sample_level", "sc_roi_thread_edges", "sc_edge_support_tables"):
-        getattr(lib, f).restype = C.c_int
+    for name, restype, argtypes in ENTRIES:
+        f = getattr(lib, name)
+        f.restype, f.argtypes = restype, argtypes
     return lib
-
-
-EXPORTS = ["sc_ctx_create", "sc_ctx_destroy", "sc_last_error", "sc_roi_error", "sc_host_plan", "sc_host_bind", "sc_roi_submit", "sc_roi_wait", "sc_roi_result",
-           "sc_roi_graph_dump", "sc_roi_trace", "sc_roi_stats", "sc_roi_release", "sc_roi_edge_support", "sc_msa_align",
-           "sc_roi_thread_tables", "sc_roi_thread_edges", "sc_edge_support_tables", "sc_sample_level", "sc_aln_open", "sc_aln_open_filtered", "sc_aln_close", "sc_aln_error", "sc_aln_records", "sc_aln_ref_stats", "sc_aln_pileup_flags",
-           "sc_aln_load_reads", "sc_reads_get", "sc_reads_free", "sc_depth_scan", "sc_depth_scan_runs", "sc_aln_walk", "sc_align_reads",
-           "sc_align_error", "sc_profile_hits", "sc_profile_error", "sc_profile_hits_seeded", "sc_profile_seed_length",
-           "sc_profile_counts", "sc_profile_index_create", "sc_profile_index_info", "sc_profile_index_counts", "sc_profile_index_free",
-           "sc_taxa_train", "sc_taxa_classify", "sc_taxa_model_counts", "sc_taxa_model_table", "sc_taxa_free", "sc_taxa_error",
-           "sc_taxa_draw"]              # (sc_profile_evalue6 as well: load_library looks it up itself; the list holds letter-only names)
-
-
-def default_params(error_rate=0.01, tau=0.02, diff_rate=0.01, graph_only=False, want_trace=False, want_timing=False, want_graph=False):
-    return ScParams(error_rate, tau, diff_rate, 5000, 40000, 80, int(graph_only), int(want_trace), int(want_timing), int(want_graph))
-
-
-def _pack(strings):
-    off = (C.c_int * (len(strings) + 1))()
-    n = 0
-    for i, s in enumerate(strings):
-        off[i] = n
-        n += len(s)
-    off[len(strings)] = n
-    return "".join(strings).encode("ascii"), off
-
-
-def host_bind(device=0):
-    """This process's main thread (and every thread started after the call) onto the CPUs next to GPU `device`; the number of
-    CPUs, 0 when nothing was changed."""
-    return int(lib().sc_host_bind(int(device)))
-
-
-def host_plan(streams, local_world=0, cpus=0.0):
-    """(executor threads, level-server threads, ingest threads) a Context(streams) starts on this host share."""
-    out = (C.c_int * 3)()
-    rc = lib().sc_host_plan(streams, local_world, cpus, out)
-    if rc != SC_OK:
-        raise StrainCallError(rc)
-    return tuple(out)
 
 
 _LIB = None
@@ -227,36 +166,112 @@ def lib():
     return _LIB
 
 
-class NativeReads:
+# ---- what the wrappers below share
+
+_PTR = {"<i4": _ip, "<i8": _lp, "<f8": _dp, "<u4": _up, "|u1": _bp, "<u8": _u64p}
+
+
+def _ptr(a):
+    """The data of a numpy array as the pointer its dtype stands for."""
+    return a.ctypes.data_as(_PTR[a.dtype.str])
+
+
+def _pack(strings):
+    off = (C.c_int * (len(strings) + 1))()
+    n = 0
+    for i, s in enumerate(strings):
+        off[i] = n
+        n += len(s)
+    off[len(strings)] = n
+    return "".join(strings).encode("ascii"), off
+
+
+def _pack_long(seqs):
+    """A list of bytes as (the text back to back, its int64 offsets)."""
+    import numpy as np
+    return b"".join(seqs), np.array([0] + [len(x) for x in seqs], dtype=np.int64).cumsum()
+
+
+def with_room(cap, attempt):
+    """The entries that answer SC_ERR_CAPACITY with the number that suffices: attempt(cap) sets room for `cap` results aside,
+    calls, and returns (rc, the number the call reports, what the caller keeps); it is repeated with the reported number while
+    that is the answer.  Returns the last attempt's triple."""
+    while True:
+        rc, n, kept = attempt(cap)
+        if rc != SC_ERR_CAPACITY or n <= cap:
+            return rc, n, kept
+        cap = n
+
+
+def _check(rc, message=None):
+    """StrainCallError unless rc is SC_OK; message: the entry that returns the calling thread's last message."""
+    if rc != SC_OK:
+        raise StrainCallError(rc, message().decode() if message else "")
+
+
+class Handle:
+    """Owner of one handle of the library, `_h`, given back by the entry `_free` names: on close(), at the end of a `with`
+    block, or with the object."""
+    _free = None
+    _h = None
+
+    def close(self):
+        if self._h:
+            try:
+                getattr(lib(), self._free)(self._h)
+            except TypeError:          # interpreter shutdown: the module globals are gone, the process frees the memory
+                pass
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def default_params(error_rate=0.01, tau=0.02, diff_rate=0.01, graph_only=False, want_trace=False, want_timing=False, want_graph=False):
+    return ScParams(error_rate, tau, diff_rate, 5000, 40000, 80, int(graph_only), int(want_trace), int(want_timing), int(want_graph))
+
+
+def host_bind(device=0):
+    """This process's main thread (and every thread started after the call) onto the CPUs next to GPU `device`; the number of
+    CPUs, 0 when nothing was changed."""
+    return int(lib().sc_host_bind(int(device)))
+
+
+def host_plan(streams, local_world=0, cpus=0.0):
+    """(executor threads, level-server threads, ingest threads) a Context(streams) starts on this host share."""
+    out = (C.c_int * 3)()
+    rc = lib().sc_host_plan(streams, local_world, cpus, out)
+    _check(rc)
+    return tuple(out)
+
+
+class NativeReads(Handle):
     """A window's reads as load_mapping_reads leaves them (rows a2-a4), held by the library as the packed arrays
     sc_roi_submit takes.  The list views (pos, cigar, seq, copies, mates) are built on demand, for tests and tools."""
+    _free = "sc_reads_free"
 
     def __init__(self, handle, gene_seq):
         self._h = handle
         self.gene_seq = gene_seq
         n, depth, n_in = C.c_int(), C.c_int(), C.c_long()
-        ip = C.POINTER(C.c_int)
-        self._pos, self._cig_off, self._seq_off, self._cn, self._mate_idx, self._mate_off = ip(), ip(), ip(), ip(), ip(), ip()
+        self._pos, self._cig_off, self._seq_off, self._cn, self._mate_idx, self._mate_off = _ip(), _ip(), _ip(), _ip(), _ip(), _ip()
         self._cig, self._seq = C.c_char_p(), C.c_char_p()
         rc = lib().sc_reads_get(handle, C.byref(n), C.byref(self._pos), C.byref(self._cig), C.byref(self._cig_off), C.byref(self._seq),
                                 C.byref(self._seq_off), C.byref(self._cn), C.byref(self._mate_idx), C.byref(self._mate_off),
                                 C.byref(n_in), C.byref(depth))
-        if rc != SC_OK:
-            raise StrainCallError(rc)
+        _check(rc)
         self.n = n.value
         self.n_input = n_in.value          # alignments the view returned for the window
         self.depth = depth.value
 
     def __len__(self):
         return self.n
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                lib().sc_reads_free(self._h)
-            except TypeError:          # interpreter shutdown: the module globals are gone, the process frees the memory
-                pass
-            self._h = None
 
     def _texts(self, text, off):
         raw = C.string_at(text, off[self.n]) if self.n else b""
@@ -290,8 +305,9 @@ class NativeReads:
         return self._view("mates", lambda: [[self._mate_idx[k] for k in range(self._mate_off[i], self._mate_off[i + 1])] for i in range(self.n)])
 
 
-class NativeAln:
+class NativeAln(Handle):
     """An alignment file (SAM text or BAM) read and indexed by the library (sc_aln_*)."""
+    _free = "sc_aln_close"
 
     def __init__(self, path, only=None):
         """only: keep the records of these references only ([]: of none -- statistics for pricing the regions; None: all)."""
@@ -307,17 +323,6 @@ class NativeAln:
             self.close()
             raise StrainCallError(rc, "%s: %s" % (path, msg))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            try:
-                lib().sc_aln_close(self._h)
-            except TypeError:          # interpreter shutdown
-                pass
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        self.close()
-
     def records(self):
         return lib().sc_aln_records(self._h)
 
@@ -327,7 +332,7 @@ class NativeAln:
         first, n_out, used = 0, C.c_long(), C.c_long()
         while True:
             rc = lib().sc_aln_walk(self._h, first, 1 << 20, buf, len(buf), C.byref(n_out), C.byref(used))
-            if rc == -5:
+            if rc == SC_ERR_CAPACITY:
                 buf = C.create_string_buffer(len(buf) * 4)
                 continue
             if rc != SC_OK:
@@ -352,11 +357,8 @@ class NativeAln:
         if n <= 0:
             return {}
         cov, ins, dele = (np.zeros(n, dtype=np.uint8) for _ in range(3))
-        pu = C.POINTER(C.c_ubyte)
-        rc = lib().sc_aln_pileup_flags(self._h, gene.encode(), P, Q, mq, cov.ctypes.data_as(pu), ins.ctypes.data_as(pu),
-                                       dele.ctypes.data_as(pu))
-        if rc != SC_OK:
-            raise StrainCallError(rc)
+        rc = lib().sc_aln_pileup_flags(self._h, gene.encode(), P, Q, mq, _ptr(cov), _ptr(ins), _ptr(dele))
+        _check(rc)
         idx = np.nonzero(cov)[0]
         return {int(k) + P: (bool(ins[k]), bool(dele[k])) for k in idx}
 
@@ -381,7 +383,7 @@ class Context:
     """One HIP device, `streams` regions in flight."""
 
     def __init__(self, device=0, streams=1):
-        self.lib = load_library()
+        self.lib = lib()
         self.h = C.c_void_p()
         rc = self.lib.sc_ctx_create(device, streams, C.byref(self.h))
         if rc != SC_OK:
@@ -406,24 +408,20 @@ class Context:
         """region: ingest.RegionReads or NativeReads.  Returns a handle."""
         n = len(region)
         if isinstance(region, NativeReads):
-            ref = region.gene_seq.encode("ascii")
-            handle = C.c_int()
-            rc = self.lib.sc_roi_submit(self.h, ref, len(ref), region._pos, region._cig, region._cig_off, region._seq, region._seq_off,
-                                        region._cn, region._mate_idx, region._mate_off, n, C.byref(params), C.byref(handle))
-            if rc != SC_OK:
-                raise self._err(rc)
-            return handle.value
-        pos = (C.c_int * max(n, 1))(*region.pos)
-        cn = (C.c_int * max(n, 1))(*region.copies)
-        cig, cig_off = _pack(region.cigar)
-        seq, seq_off = _pack(region.seq)
-        mate_off = (C.c_int * (n + 1))()
-        flat = []
-        for i, m in enumerate(region.mates):
-            mate_off[i] = len(flat)
-            flat.extend(m)
-        mate_off[n] = len(flat)
-        mate_idx = (C.c_int * max(len(flat), 1))(*flat)
+            pos, cig, cig_off, seq, seq_off = region._pos, region._cig, region._cig_off, region._seq, region._seq_off
+            cn, mate_idx, mate_off = region._cn, region._mate_idx, region._mate_off
+        else:
+            pos = (C.c_int * max(n, 1))(*region.pos)
+            cn = (C.c_int * max(n, 1))(*region.copies)
+            cig, cig_off = _pack(region.cigar)
+            seq, seq_off = _pack(region.seq)
+            mate_off = (C.c_int * (n + 1))()
+            flat = []
+            for i, m in enumerate(region.mates):
+                mate_off[i] = len(flat)
+                flat.extend(m)
+            mate_off[n] = len(flat)
+            mate_idx = (C.c_int * max(len(flat), 1))(*flat)
         ref = region.gene_seq.encode("ascii")
         handle = C.c_int()
         rc = self.lib.sc_roi_submit(self.h, ref, len(ref), pos, cig, cig_off, seq, seq_off, cn, mate_idx, mate_off, n,
@@ -457,7 +455,7 @@ class Context:
             off = (C.c_int * (maxs + 1))()
             ab = (C.c_double * maxs)()
             rc = self.lib.sc_roi_result(self.h, handle, buf, cap, off, ab, maxs, C.byref(nst))
-            if rc == -5 and cap < (1 << 30):
+            if rc == SC_ERR_CAPACITY and cap < (1 << 30):
                 cap *= 8
                 maxs *= 4
                 continue
@@ -520,11 +518,8 @@ class Context:
         end = np.ascontiguousarray(node_is_end, dtype=np.uint8)
         assert rid.shape == cn.shape and src.shape == dst.shape and ptr_.size == end.size + 1
         out = np.zeros(max(src.size, 1), dtype=np.int32)
-
-        def ptr(x):
-            return x.ctypes.data_as(C.POINTER(C.c_ubyte if x.dtype == np.uint8 else C.c_int))
-        rc = self.lib.sc_edge_support_tables(self.h, end.size, ptr(ptr_), ptr(rid), ptr(cn), ptr(end), src.size, ptr(src), ptr(dst),
-                                             int(sorted_pools), ptr(out))
+        rc = self.lib.sc_edge_support_tables(self.h, end.size, _ptr(ptr_), _ptr(rid), _ptr(cn), _ptr(end), src.size, _ptr(src), _ptr(dst),
+                                             int(sorted_pools), _ptr(out))
         if rc != SC_OK:
             raise self._err(rc)
         return out[:src.size].tolist()
@@ -549,13 +544,8 @@ class Context:
         kdraw = np.zeros(S, dtype=np.uint32)
         cnt = np.zeros((S, 16), dtype=np.uint32)
         out = (C.c_long * 6)()
-
-        def ptr(x, t):
-            return x.ctypes.data_as(C.POINTER(t))
-        rc = self.lib.sc_sample_level(self.h, S, ptr(a0, C.c_double), n_reads, ptr(ll, C.c_double), ptr(has, C.c_ubyte),
-                                      len(ent[0]), e0, ptr(ent[0], C.c_int), ptr(ent[1], C.c_int), ptr(ent[2], C.c_int),
-                                      ptr(mate_off, C.c_int), ptr(mate_idx, C.c_int), n_sweeps, ptr(U, C.c_double), len(U),
-                                      ptr(kdraw, C.c_uint), ptr(cnt, C.c_uint), out)
+        rc = self.lib.sc_sample_level(self.h, S, _ptr(a0), n_reads, _ptr(ll), _ptr(has), len(ent[0]), e0, _ptr(ent[0]), _ptr(ent[1]),
+                                      _ptr(ent[2]), _ptr(mate_off), _ptr(mate_idx), n_sweeps, _ptr(U), len(U), _ptr(kdraw), _ptr(cnt), out)
         if rc != SC_OK:
             raise self._err(rc)
         return dict(kdraw=kdraw, cnt=cnt, n_draws=out[0], n_slow=out[1], n_exact=out[2], n_pass=out[3], kind=out[4], done=out[5])
@@ -585,8 +575,8 @@ def align_reads(seeds, reads, quals=None, device=0):
     lists of bytes (quals None, or an entry b"*": Q40)."""
     import numpy as np
     n = len(reads)
-    sl = np.array([0] + [len(x) for x in seeds], dtype=np.int64).cumsum()
-    rl = np.array([0] + [len(x) for x in reads], dtype=np.int64).cumsum()
+    stext, sl = _pack_long(seeds)
+    rtext, rl = _pack_long(reads)
     qtext = None
     if quals is not None:
         qtext = b"".join(q if (q != b"*" and len(q) == len(r)) else b"I" * len(r) for r, q in zip(reads, quals))
@@ -594,13 +584,9 @@ def align_reads(seeds, reads, quals=None, device=0):
     as_, xs, seed, strand, pos, nm, ncig = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(7))
     cig = np.zeros(max(n, 1) * stride, dtype=np.uint32)
     st = ScAlignStats()
-    ip, lp, up = C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_uint)
-    rc = lib().sc_align_reads(device, b"".join(seeds), sl.ctypes.data_as(lp), len(seeds), b"".join(reads), qtext, rl.ctypes.data_as(lp), n,
-                              as_.ctypes.data_as(ip), xs.ctypes.data_as(ip), seed.ctypes.data_as(ip), strand.ctypes.data_as(ip),
-                              pos.ctypes.data_as(ip), nm.ctypes.data_as(ip), cig.ctypes.data_as(up), stride, ncig.ctypes.data_as(ip),
-                              C.byref(st))
-    if rc != SC_OK:
-        raise StrainCallError(rc, lib().sc_align_error().decode())
+    rc = lib().sc_align_reads(device, stext, _ptr(sl), len(seeds), rtext, qtext, _ptr(rl), n, _ptr(as_), _ptr(xs), _ptr(seed), _ptr(strand),
+                              _ptr(pos), _ptr(nm), _ptr(cig), stride, _ptr(ncig), C.byref(st))
+    _check(rc, lib().sc_align_error)
     cigars = []
     for r in range(n):
         ops = cig[r * stride:r * stride + ncig[r]]
@@ -624,26 +610,21 @@ class ProfileHits:
 
 def _profile_call(gtext, gl, n_genes, segs, thresholds, device, cap, seeded=False):
     import numpy as np
-    n = len(segs)
-    sl = np.array([0] + [len(x) for x in segs], dtype=np.int64).cumsum()
-    stext = b"".join(segs)
-    ip, lp, dp = C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_double)
-    while True:
+    stext, sl = _pack_long(segs)
+    entry, stats = (lib().sc_profile_hits_seeded, ScProfileSeedStats) if seeded else (lib().sc_profile_hits, ScProfileStats)
+
+    def attempt(cap):
         ints = [np.zeros(max(cap, 1), dtype=np.int32) for _ in range(9)]
         score, ev = np.zeros(max(cap, 1), dtype=np.float64), np.zeros(max(cap, 1), dtype=np.float64)
-        st, nh = (ScProfileSeedStats if seeded else ScProfileStats)(), C.c_long()
-        iptr = [a.ctypes.data_as(ip) for a in ints]
-        rc = (lib().sc_profile_hits_seeded if seeded else lib().sc_profile_hits)(device, gtext, gl.ctypes.data_as(lp), n_genes, stext, sl.ctypes.data_as(lp), n, *thresholds, iptr[0],
-                                   iptr[1], iptr[2], score.ctypes.data_as(dp), iptr[3], iptr[4], iptr[5], iptr[6], iptr[7], iptr[8],
-                                   ev.ctypes.data_as(dp), cap, C.byref(nh), C.byref(st))
-        if rc == -5 and nh.value > cap:
-            cap = nh.value
-            continue
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_profile_error().decode())
-        k = nh.value
-        seg, gene, strand, identity, align_len, qfrom, qto, hfrom, hto = (a[:k] for a in ints)
-        return [seg, gene, strand, score[:k], identity, align_len, qfrom, qto, hfrom, hto, ev[:k]], st
+        st, nh = stats(), C.c_long()
+        iptr = [_ptr(a) for a in ints]
+        rc = entry(device, gtext, _ptr(gl), n_genes, stext, _ptr(sl), len(segs), *thresholds, iptr[0], iptr[1], iptr[2], _ptr(score),
+                   iptr[3], iptr[4], iptr[5], iptr[6], iptr[7], iptr[8], _ptr(ev), cap, C.byref(nh), C.byref(st))
+        return rc, nh.value, (ints, score, ev, st)
+    rc, k, (ints, score, ev, st) = with_room(cap, attempt)
+    _check(rc, lib().sc_profile_error)
+    seg, gene, strand, identity, align_len, qfrom, qto, hfrom, hto = (a[:k] for a in ints)
+    return [seg, gene, strand, score[:k], identity, align_len, qfrom, qto, hfrom, hto, ev[:k]], st
 
 
 def profile_seed_length(seg_lens, gene_bases, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, lossless=False):
@@ -653,7 +634,7 @@ def profile_seed_length(seg_lens, gene_bases, min_identity=95.0, max_evalue=1e-1
     import numpy as np
     lens = np.ascontiguousarray(seg_lens, dtype=np.int32)
     raw = C.c_int()
-    k = lib().sc_profile_seed_length(lens.ctypes.data_as(C.POINTER(C.c_int)), len(lens), int(gene_bases), float(min_identity), float(max_evalue),
+    k = lib().sc_profile_seed_length(_ptr(lens), len(lens), int(gene_bases), float(min_identity), float(max_evalue),
                                      float(ka_lambda), float(ka_k), C.byref(raw))
     if k < 0:
         raise StrainCallError(k)
@@ -669,8 +650,7 @@ def profile_hits(genes, segs, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.2
     ScProfileSeedStats, the genes are indexed again per stretch, and seed_k is the smallest of the stretches' (0 as soon as one
     ran unseeded)."""
     import numpy as np
-    gl = np.array([0] + [len(x) for x in genes], dtype=np.int64).cumsum()
-    gtext = b"".join(genes)
+    gtext, gl = _pack_long(genes)
     thresholds = (float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k))
     step = max(1, (1 << 30) // (2 * max(len(genes), 1)))
     parts, total, seed_ks = [], (ScProfileSeedStats if seeded else ScProfileStats)(), []
@@ -707,37 +687,36 @@ def profile_evalue6(seg_len, gene_bases, score2, ka_lambda=1.28, ka_k=0.46):
     return float(lib().sc_profile_evalue6(int(seg_len), int(gene_bases), int(score2), float(ka_lambda), float(ka_k)))
 
 
+def _count_rows(entry, lead, segs, seg_read, read_args, options, cap, n_cols, stats):
+    """What sc_profile_counts and sc_profile_index_counts share: entry(*lead, the segments, their read indices,
+    *read_args(read indices), *options, n_cols int32 columns, the reads column, cap, n, statistics).  Returns (the rows as
+    tuples, the statistics)."""
+    import numpy as np
+    stext, sl = _pack_long(segs)
+    reads = np.ascontiguousarray(seg_read, dtype=np.int32)
+    if len(reads) != len(segs):
+        raise ValueError("%d read indices for %d segments" % (len(reads), len(segs)))
+    args = list(lead) + [stext, _ptr(sl), len(segs), _ptr(reads)] + read_args(reads) + list(options)
+
+    def attempt(cap):
+        cols = [np.zeros(max(cap, 1), dtype=np.int32) for _ in range(n_cols)] + [np.zeros(max(cap, 1), dtype=np.int64)]
+        st, n = stats(), C.c_long()
+        return entry(*args, *[_ptr(c) for c in cols], cap, C.byref(n), C.byref(st)), n.value, (cols, st)
+    rc, k, (cols, st) = with_room(1 << 16 if cap is None else int(cap), attempt)
+    _check(rc, lib().sc_profile_error)
+    return list(zip(*(c[:k].tolist() for c in cols))), st
+
+
 def profile_counts(genes, segs, seg_read, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, device=0, cap=None, seeded=False,
                    cand_room=0):
     """sc_profile_counts: the counting rule over the hits of profile_hits without the hit list.  genes, segs:
     lists of bytes; seg_read: one read index per segment (profile.read_index).  The room for triples starts at `cap`
     (default 65 536) and grows to what the library asks for.  The library itself passes the segments through in stretches of
     whole reads that fit `cand_room` candidate records (0: its default); the genes are uploaded and indexed once."""
-    import numpy as np
-    gl = np.array([0] + [len(x) for x in genes], dtype=np.int64).cumsum()
-    sl = np.array([0] + [len(x) for x in segs], dtype=np.int64).cumsum()
-    gtext, stext = b"".join(genes), b"".join(segs)
-    reads = np.ascontiguousarray(seg_read, dtype=np.int32)
-    if len(reads) != len(segs):
-        raise ValueError("%d read indices for %d segments" % (len(reads), len(segs)))
-    n_reads = int(reads.max()) + 1 if len(reads) else 0
-    ip, lp = C.POINTER(C.c_int), C.POINTER(C.c_long)
-    cap = 1 << 16 if cap is None else int(cap)
-    while True:
-        gene, times, share = (np.zeros(max(cap, 1), dtype=np.int32) for _ in range(3))
-        n_behind = np.zeros(max(cap, 1), dtype=np.int64)
-        st, n = ScProfileCountStats(), C.c_long()
-        rc = lib().sc_profile_counts(device, gtext, gl.ctypes.data_as(lp), len(genes), stext, sl.ctypes.data_as(lp), len(segs),
-                                     reads.ctypes.data_as(ip), n_reads, float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k),
-                                     int(bool(seeded)), int(cand_room), gene.ctypes.data_as(ip), times.ctypes.data_as(ip),
-                                     share.ctypes.data_as(ip), n_behind.ctypes.data_as(lp), cap, C.byref(n), C.byref(st))
-        if rc == -5 and n.value > cap:
-            cap = n.value
-            continue
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_profile_error().decode())
-        k = n.value
-        return ProfileCounts([(int(gene[i]), int(times[i]), int(share[i]), int(n_behind[i])) for i in range(k)], st)
+    gtext, gl = _pack_long(genes)
+    options = (float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k), int(bool(seeded)), int(cand_room))
+    return ProfileCounts(*_count_rows(lib().sc_profile_counts, (device, gtext, _ptr(gl), len(genes)), segs, seg_read,
+                                      lambda reads: [int(reads.max()) + 1 if len(reads) else 0], options, cap, 3, ScProfileCountStats))
 
 
 class ProfileCohortCounts:
@@ -756,35 +735,17 @@ class ProfileCohortCounts:
         return [r[1:] for r in self.rows if r[0] == s]
 
 
-class ProfileIndex:
+class ProfileIndex(Handle):
     """The genes of a cohort held on one device until close() (sc_profile_index_create): uploaded once, with
     the k-mer keys of every seed length a call has needed and the arrays the calls work in.  genes: a list of bytes.  One
     call at a time."""
+    _free = "sc_profile_index_free"
 
     def __init__(self, genes, device=0):
-        import numpy as np
-        gl = np.array([0] + [len(x) for x in genes], dtype=np.int64).cumsum()
+        gtext, gl = _pack_long(genes)
         self._h = C.c_void_p()
-        rc = lib().sc_profile_index_create(int(device), b"".join(genes), gl.ctypes.data_as(C.POINTER(C.c_long)), len(genes), C.byref(self._h))
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_profile_error().decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            try:
-                lib().sc_profile_index_free(self._h)
-            except TypeError:          # interpreter shutdown
-                pass
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        rc = lib().sc_profile_index_create(int(device), gtext, _ptr(gl), len(genes), C.byref(self._h))
+        _check(rc, lib().sc_profile_error)
 
     def info(self):
         """sc_profile_index_info: {"n_genes", "gene_bases", "cached_k": the seed lengths whose keys are kept, ascending}."""
@@ -792,8 +753,7 @@ class ProfileIndex:
             raise ValueError("the index is closed")
         n_genes, bases, n_k, ks = C.c_int(), C.c_long(), C.c_int(), (C.c_int * 6)()
         rc = lib().sc_profile_index_info(self._h, C.byref(n_genes), C.byref(bases), C.byref(n_k), ks)
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_profile_error().decode())
+        _check(rc, lib().sc_profile_error)
         return {"n_genes": n_genes.value, "gene_bases": bases.value, "cached_k": [int(ks[i]) for i in range(n_k.value)]}
 
     def counts(self, segs, seg_read, read_sample, n_samples, min_identity=95.0, max_evalue=1e-10, ka_lambda=1.28, ka_k=0.46, cap=None,
@@ -804,32 +764,15 @@ class ProfileIndex:
         import numpy as np
         if not self._h:
             raise ValueError("the index is closed")
-        sl = np.array([0] + [len(x) for x in segs], dtype=np.int64).cumsum()
-        stext = b"".join(segs)
-        reads = np.ascontiguousarray(seg_read, dtype=np.int32)
         samples = np.ascontiguousarray(read_sample, dtype=np.int32)
-        if len(reads) != len(segs):
-            raise ValueError("%d read indices for %d segments" % (len(reads), len(segs)))
-        if len(reads) and int(reads.max()) >= len(samples):
-            raise ValueError("read %d of %d reads with a sample" % (int(reads.max()), len(samples)))
-        ip, lp = C.POINTER(C.c_int), C.POINTER(C.c_long)
-        cap = 1 << 16 if cap is None else int(cap)
-        while True:
-            sample, gene, times, share = (np.zeros(max(cap, 1), dtype=np.int32) for _ in range(4))
-            n_behind = np.zeros(max(cap, 1), dtype=np.int64)
-            st, n = ScProfileCohortStats(), C.c_long()
-            rc = lib().sc_profile_index_counts(self._h, stext, sl.ctypes.data_as(lp), len(segs), reads.ctypes.data_as(ip), len(samples),
-                                               samples.ctypes.data_as(ip), int(n_samples), float(min_identity), float(max_evalue),
-                                               float(ka_lambda), float(ka_k), int(bool(seeded)), int(cand_room), sample.ctypes.data_as(ip),
-                                               gene.ctypes.data_as(ip), times.ctypes.data_as(ip), share.ctypes.data_as(ip),
-                                               n_behind.ctypes.data_as(lp), cap, C.byref(n), C.byref(st))
-            if rc == -5 and n.value > cap:
-                cap = n.value
-                continue
-            if rc != SC_OK:
-                raise StrainCallError(rc, lib().sc_profile_error().decode())
-            return ProfileCohortCounts([(int(sample[i]), int(gene[i]), int(times[i]), int(share[i]), int(n_behind[i])) for i in range(n.value)],
-                                       st)
+
+        def read_args(reads):
+            if len(reads) and int(reads.max()) >= len(samples):
+                raise ValueError("read %d of %d reads with a sample" % (int(reads.max()), len(samples)))
+            return [len(samples), _ptr(samples), int(n_samples)]
+        options = (float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k), int(bool(seeded)), int(cand_room))
+        return ProfileCohortCounts(*_count_rows(lib().sc_profile_index_counts, (self._h,), segs, seg_read, read_args, options, cap, 4,
+                                                ScProfileCohortStats))
 
 
 TAXA_WORDS = 65536
@@ -841,16 +784,12 @@ def taxa_draw(seed, key, trial, draw, n_words):
     return int(lib().sc_taxa_draw(int(seed), int(key), int(trial), int(draw), int(n_words)))
 
 
-def _pack_long(seqs):
-    import numpy as np
-    return b"".join(seqs), np.array([0] + [len(x) for x in seqs], dtype=np.int64).cumsum()
-
-
-class TaxaModel:
+class TaxaModel(Handle):
     """A model trained by sc_taxa_train, held on one device until close().  seqs: the training sequences
     (bytes), genus: one genus index in 0..n_genera-1 per sequence.  grid_cap bounds the blocks of every launch (0: the
     library's own bound); keep_counts: also keep m for counts(), as much device memory again; stats is the ScTaxaStats of the
     training."""
+    _free = "sc_taxa_free"
 
     def __init__(self, seqs, genus, n_genera, device=0, grid_cap=0, keep_counts=False):
         import numpy as np
@@ -861,27 +800,9 @@ class TaxaModel:
         self.n_genera = int(n_genera)
         self._h = C.c_void_p()
         self.stats = ScTaxaStats()
-        rc = lib().sc_taxa_train(int(device), text, off.ctypes.data_as(C.POINTER(C.c_long)), len(seqs), gi.ctypes.data_as(C.POINTER(C.c_int)),
-                                 self.n_genera, int(grid_cap), int(bool(keep_counts)), C.byref(self._h), C.byref(self.stats))
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_taxa_error().decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            try:
-                lib().sc_taxa_free(self._h)
-            except TypeError:          # interpreter shutdown
-                pass
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        rc = lib().sc_taxa_train(int(device), text, _ptr(off), len(seqs), _ptr(gi), self.n_genera, int(grid_cap), int(bool(keep_counts)),
+                                 C.byref(self._h), C.byref(self.stats))
+        _check(rc, lib().sc_taxa_error)
 
     def classify(self, queries, keys, seed=0, n_trials=TAXA_TRIALS, grid_cap=0):
         """sc_taxa_classify: queries (bytes) with one 64-bit key each.  Returns (best_genus[n], trial_winner[n][n_trials],
@@ -895,29 +816,23 @@ class TaxaModel:
         best, words = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
         winner = np.zeros((max(n, 1), max(int(n_trials), 1)), dtype=np.int32)
         st = ScTaxaStats()
-        ip = C.POINTER(C.c_int)
-        rc = lib().sc_taxa_classify(self._h, text, off.ctypes.data_as(C.POINTER(C.c_long)), n, key.ctypes.data_as(C.POINTER(C.c_ulonglong)),
-                                    int(seed), int(n_trials), int(grid_cap), best.ctypes.data_as(ip), winner.ctypes.data_as(ip),
-                                    words.ctypes.data_as(ip), C.byref(st))
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_taxa_error().decode())
+        rc = lib().sc_taxa_classify(self._h, text, _ptr(off), n, _ptr(key), int(seed), int(n_trials), int(grid_cap), _ptr(best),
+                                    _ptr(winner), _ptr(words), C.byref(st))
+        _check(rc, lib().sc_taxa_error)
         return best[:n], winner[:n], words[:n], st
 
     def counts(self, genus):
         """sc_taxa_model_counts: (m of the genus, n), 65 536 uint32 each; of a model trained with keep_counts."""
         import numpy as np
         m, n = np.zeros(TAXA_WORDS, dtype=np.uint32), np.zeros(TAXA_WORDS, dtype=np.uint32)
-        up = C.POINTER(C.c_uint)
-        rc = lib().sc_taxa_model_counts(self._h, int(genus), m.ctypes.data_as(up), n.ctypes.data_as(up))
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_taxa_error().decode())
+        rc = lib().sc_taxa_model_counts(self._h, int(genus), _ptr(m), _ptr(n))
+        _check(rc, lib().sc_taxa_error)
         return m, n
 
     def table(self, genus):
         """sc_taxa_model_table: the genus' column of the table, 65 536 int32."""
         import numpy as np
         q = np.zeros(TAXA_WORDS, dtype=np.int32)
-        rc = lib().sc_taxa_model_table(self._h, int(genus), q.ctypes.data_as(C.POINTER(C.c_int)))
-        if rc != SC_OK:
-            raise StrainCallError(rc, lib().sc_taxa_error().decode())
+        rc = lib().sc_taxa_model_table(self._h, int(genus), _ptr(q))
+        _check(rc, lib().sc_taxa_error)
         return q

@@ -25,9 +25,7 @@ def _numeric_key(name):
     return int(m.group(1)) if m else 0
 
 
-class DepthStats(C.Structure):
-    _fields_ = [("cells", C.c_long), ("runs", C.c_long), ("extract_ms", C.c_double), ("prepare_ms", C.c_double),
-                ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+DepthStats = capi.ScDepthStats
 
 
 def depth_intervals(paths, fai_path, max_gap=10, device=0, alns=None):
@@ -40,12 +38,8 @@ def depth_intervals(paths, fai_path, max_gap=10, device=0, alns=None):
     names = (C.c_char_p * max(n_refs, 1))(*[n.encode() for n, _ in refs])
     lens = (C.c_int * max(n_refs, 1))(*[l for _, l in refs])
     handles = (C.c_void_p * max(len(alns), 1))(*[a._h for a in alns])
-    lib.sc_depth_scan.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int,
-                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_int),
-                                  C.c_int, C.POINTER(C.c_int), C.POINTER(DepthStats)]
-    lib.sc_depth_scan.restype = C.c_int
-    cap = max(4 * n_refs, 1024)
-    while True:
+
+    def attempt(cap):
         iv = [(C.c_int * cap)() for _ in range(3)]
         sm = (C.c_long * cap)()
         cn = (C.c_int * cap)()
@@ -53,14 +47,12 @@ def depth_intervals(paths, fai_path, max_gap=10, device=0, alns=None):
         st = DepthStats()
         rc = lib.sc_depth_scan(device, handles, len(alns), names, lens, n_refs, max_gap, iv[0], iv[1], iv[2], sm, cn, cap, C.byref(n),
                                C.byref(st))
-        if rc == -5 and n.value > cap:
-            cap = n.value
-            continue
-        if rc != capi.SC_OK:
-            raise capi.StrainCallError(rc, "sc_depth_scan")
-        break
-    out = [(refs[iv[0][i]][0], iv[1][i], iv[2][i], sm[i], cn[i]) for i in range(n.value)]
-    return out, {k: getattr(st, k) for k, _ in DepthStats._fields_}
+        return rc, n.value, (iv, sm, cn, st)
+    rc, n, (iv, sm, cn, st) = capi.with_room(max(4 * n_refs, 1024), attempt)
+    if rc != capi.SC_OK:
+        raise capi.StrainCallError(rc, "sc_depth_scan")
+    out = [(refs[iv[0][i]][0], iv[1][i], iv[2][i], sm[i], cn[i]) for i in range(n)]
+    return out, st.as_dict()
 
 
 def bed_text(intervals):

@@ -409,9 +409,6 @@ def scan_runs(ref_len, run_ref, run_start, run_end, max_gap, cap, n_before=-7):
     from rambl_amd import capi, stage1
     lib = capi.lib()
     ip, lp = C.POINTER(C.c_int), C.POINTER(C.c_long)
-    lib.sc_depth_scan_runs.argtypes = [C.c_int, ip, C.c_int, ip, ip, ip, C.c_long, C.c_int, ip, ip, ip, lp, ip, C.c_int, ip,
-                                       C.POINTER(stage1.DepthStats)]
-    lib.sc_depth_scan_runs.restype = C.c_int
 
     def padded(a):                                 # never a null pointer, whatever the length
         a = np.asarray(a, dtype=np.int32).reshape(-1)

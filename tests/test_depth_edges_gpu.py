@@ -81,10 +81,6 @@ def test_extreme_max_gap():
     handles = (C.c_void_p * 1)()
     out = [(C.c_int * 4)() for _ in range(4)]
     sm = (C.c_long * 4)()
-    lib.sc_depth_scan.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int,
-                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_int),
-                                  C.c_int, C.POINTER(C.c_int), C.POINTER(stage1.DepthStats)]
-    lib.sc_depth_scan.restype = C.c_int
     for g, rc in ((D.MAX_GAP_LIMIT, D.SC_OK), (D.MAX_GAP_LIMIT + 1, D.SC_ERR_ARG), (2 ** 31 - 1, D.SC_ERR_ARG)):
         n = C.c_int(-7)
         st = stage1.DepthStats()

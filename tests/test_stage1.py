@@ -113,8 +113,6 @@ def test_depth_scan_large_property(tmp_path):
     cn = np.zeros(cap, dtype=np.int32)
     n = C.c_int()
     st = stage1.DepthStats()
-    lib.sc_depth_scan_runs.argtypes = [C.c_int, ip, C.c_int, ip, ip, ip, C.c_long, C.c_int, ip, ip, ip, C.POINTER(C.c_long), ip, C.c_int, ip,
-                                       C.POINTER(stage1.DepthStats)]
     rc = lib.sc_depth_scan_runs(0, ref_len.ctypes.data_as(ip), n_refs, run_ref.ctypes.data_as(ip), start.ctypes.data_as(ip),
                                 end.ctypes.data_as(ip), n_runs, 10, iv[0].ctypes.data_as(ip), iv[1].ctypes.data_as(ip),
                                 iv[2].ctypes.data_as(ip), sm.ctypes.data_as(C.POINTER(C.c_long)), cn.ctypes.data_as(ip), cap, C.byref(n),
