@@ -190,6 +190,26 @@ int sc_sample_level(sc_ctx* ctx, int S, const double* a0, int n_reads, const dou
                     int n_ent, int e0, const int* ent_rid, const int* ent_cn, const int* ent_sym, const int* mate_off,
                     const int* mate_idx, int n_sweeps, const double* U, int n_u, unsigned* kdraw, unsigned* cnt, long* out);
 
+/* Row a13 on its own, for tests: the read log-likelihood update of one level (NonparametricClustering.cpp:343-391) and the
+ * row copies in front of it (Strain.cpp:73-83), through the production level kernel and, where the level goes there, the
+ * grid kernels in front of it -- no sampler, no hard update.  S (1..128) strains: strain s owns row slot[s] (distinct,
+ * < 128) of the matrix and has the node label labels[lab_off[s] .. + lab_len[s]) and the log table lpt[s*K*K + a*K + b];
+ * K symbols (6..16), code_N the code of N (-1: none, else 6..K-1).  ll[s*n_reads + r] are the strains' rows before the
+ * level (every other row of the matrix starts as zeros), has[n_reads] the reads present.  The level's n_ent entries start
+ * at entry index e0 (the entries in front name other reads): read ent_rid, label labels[ent_lab_off .. + ent_lab_len),
+ * ent_first (0: the read occurred earlier in this level).  n_copy row copies copy_src[c] -> copy_dst[c] of the leading
+ * copy_n cells run first; a destination is no other pair's destination and nobody's source.  S*K*K fits the level
+ * kernel's log tables.  A label of one symbol may hold any code; every code of a longer label is below K (or code_N in a
+ * strain's label), and so is every entry's once a strain's label is longer than one symbol.  SC_ERR_ARG otherwise, before
+ * anything is launched, and on a context of more than one stream.  Out: ll_out[128*n_reads] the whole matrix,
+ * has_out[n_reads], isnew_out[n_ent] (the entry's read was entered by this level), *done_out the pieces of the level that
+ * ran on a grid (LV_* bits). */
+int sc_update_level(sc_ctx* ctx, int S, const int* slot, const int* lab_off, const int* lab_len, int K, int code_N,
+                    const double* lpt, int n_reads, const double* ll, const unsigned char* has, const unsigned char* labels,
+                    int n_labels, int n_ent, int e0, const int* ent_rid, const int* ent_lab_off, const int* ent_lab_len,
+                    const unsigned char* ent_first, int n_copy, const int* copy_src, const int* copy_dst, int copy_n,
+                    double* ll_out, unsigned char* has_out, unsigned char* isnew_out, int* done_out);
+
 /* ---- rows a2-a4 on the host: the alignment file and a window's reads (rambl_amd/csrc/sc_ingest.cpp) ----------
  *
  * The reference shells out to samtools for every window (StrainCall.cpp:496 `view -q mq -F 1804 region`, :696

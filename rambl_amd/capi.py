@@ -107,6 +107,8 @@ ENTRIES = [
     ("sc_roi_thread_edges", _i, [_vp, _i, _ip, _ip, _ip, _i, _ip]),
     ("sc_edge_support_tables", _i, [_vp, _i, _ip, _ip, _ip, _bp, _i, _ip, _ip, _i, _ip]),
     ("sc_sample_level", _i, [_vp, _i, _dp, _i, _dp, _bp, _i, _i, _ip, _ip, _ip, _ip, _ip, _i, _dp, _i, _up, _up, _lp]),
+    ("sc_update_level", _i, [_vp, _i, _ip, _ip, _ip, _i, _i, _dp, _i, _dp, _bp, _bp, _i, _i, _i, _ip, _ip, _ip, _bp, _i, _ip, _ip, _i,
+                             _dp, _bp, _bp, _ip]),
     ("sc_aln_open", _i, [_s, _vpp]),
     ("sc_aln_open_filtered", _i, [_s, _sp, _i, _vpp]),
     ("sc_aln_close", None, [_vp]),
@@ -549,6 +551,38 @@ class Context:
         if rc != SC_OK:
             raise self._err(rc)
         return dict(kdraw=kdraw, cnt=cnt, n_draws=out[0], n_slow=out[1], n_exact=out[2], n_pass=out[3], kind=out[4], done=out[5])
+
+    def update_level(self, slot, strain_labels, K, code_N, lpt, ll, has, ent_rid, ent_labels, ent_first, copies=(), copy_n=0, e0=1):
+        """Row a13 on its own (a test entry): the row copies and the read log-likelihood update of one level through the
+        production kernels.  slot: [S] rows of the strains, strain_labels / ent_labels: per strain / entry its label as a
+        sequence of symbol codes, lpt: [S][K][K], ll: [S][n_reads] the strains' rows before the level, has: [n_reads],
+        ent_first: [n_ent] (0: the read occurred earlier in the level), copies: (source row, destination row) pairs.
+        Returns dict(ll[128][n_reads]: the whole matrix, has, isnew[n_ent], done: the pieces that ran on a grid)."""
+        import numpy as np
+        ll = np.ascontiguousarray(ll, dtype=np.float64)
+        S, n_reads = ll.shape
+        lpt = np.ascontiguousarray(lpt, dtype=np.float64)
+        assert lpt.shape == (S, K, K) and len(slot) == len(strain_labels) == S
+        has = np.ascontiguousarray(has, dtype=np.uint8)
+        assert has.shape == (n_reads,) and len(ent_rid) == len(ent_labels) == len(ent_first)
+        labels = [list(x) for x in list(strain_labels) + list(ent_labels)]
+        lab_len = np.array([len(x) for x in labels], dtype=np.int32)
+        lab_off = np.ascontiguousarray(np.concatenate(([0], np.cumsum(lab_len)[:-1])), dtype=np.int32)
+        codes = np.array([c for x in labels for c in x] or [0], dtype=np.uint8)
+        slot, rid = (np.ascontiguousarray(x, dtype=np.int32) for x in (slot, ent_rid))
+        first = np.ascontiguousarray(ent_first, dtype=np.uint8)
+        src, dst = (np.array([p[k] for p in copies] or [0], dtype=np.int32) for k in (0, 1))
+        s_off, s_len, e_off, e_len = (np.ascontiguousarray(x) for x in (lab_off[:S], lab_len[:S], lab_off[S:], lab_len[S:]))
+        ll_out = np.zeros((128, n_reads), dtype=np.float64)
+        has_out = np.zeros(n_reads, dtype=np.uint8)
+        isnew = np.zeros(max(len(rid), 1), dtype=np.uint8)
+        done = C.c_int()
+        rc = self.lib.sc_update_level(self.h, S, _ptr(slot), _ptr(s_off), _ptr(s_len), K, code_N, _ptr(lpt), n_reads, _ptr(ll), _ptr(has),
+                                      _ptr(codes), len(codes), len(rid), e0, _ptr(rid), _ptr(e_off), _ptr(e_len), _ptr(first),
+                                      len(copies), _ptr(src), _ptr(dst), copy_n, _ptr(ll_out), _ptr(has_out), _ptr(isnew), C.byref(done))
+        if rc != SC_OK:
+            raise self._err(rc)
+        return dict(ll=ll_out, has=has_out, isnew=isnew[:len(rid)], done=done.value)
 
     def msa_align(self, seqs):
         """Row a7: rows of the progressive sum-of-pairs MSA of `seqs` (in the given order)."""

@@ -9,6 +9,49 @@
 #include "sc_ctx.hpp"
 
 using namespace sc;
+// What the one-level test entries (sc_sample_level, sc_update_level) share: a region that is nothing but one level.  Its
+// entries lie at [e0, e0 + n_ent) of the region's arrays; entries [0, e0) belong to other levels: they name other reads (the
+// last ones, backwards), so that an entry index that misses e0 reads the wrong row.  The vectors live as long as the stub:
+// the copies of a private worker pass through, so their sources stay until the stream is synchronised.
+struct LevelStub {
+    FlatGraph f;
+    std::vector<int> qoff, mptr, midx;
+    std::vector<double> rows;
+    std::vector<uint8_t> hv;
+    JobDev jd{};
+    // every entry with copy number 1, its one-symbol label at labels[e] (code 0) and `first` set; labels holds n_labels
+    // codes (> e0).  The caller then states its own entries, [e0, e0 + n_ent).
+    void entries(int e0, int n_ent, int n_reads, size_t n_labels) {
+        const size_t E = (size_t)e0 + (size_t)n_ent;
+        f.ent_rid.resize(E); f.ent_cn.assign(E, 1); f.ent_lab_off.resize(E); f.ent_lab_len.assign(E, 1); f.ent_first.assign(E, 1);
+        f.labels.assign(n_labels, 0);
+        qoff.assign(E, 0);
+        for (size_t e = 0; e < E; e++) {
+            f.ent_rid[e] = n_reads - 1 - (int)e % n_reads;
+            f.ent_lab_off[e] = (int)e;
+        }
+        mptr.assign((size_t)n_reads + 1, 0);
+        midx.clear();
+    }
+    // the region's device block (Worker::job_dev), the rows ll[s * n_reads + r] of the S strains in rows slot[s] of a
+    // matrix of zeros, `has` padded as the region set-up pads it; the caller adds what it needs (U, Uf) and publishes
+    JobDev& upload(Worker& w, int n_reads, long qcap, int n_ent, long max_draws, int S, const int* slot, const double* ll, const unsigned char* has) {
+        jd = w.job_dev(w.passthrough, f, qoff, mptr, midx, n_reads, qcap, n_ent, max_draws);
+        rows.assign((size_t)jd.ll_stride * MAXS, 0.0);
+        for (int s = 0; s < S; s++) std::memcpy(&rows[(size_t)slot[s] * jd.ll_stride], ll + (size_t)s * n_reads, sizeof(double) * n_reads);
+        jd.ll = sc::upload(w.passthrough, w.b_ll, rows, w.st);
+        hv.assign(has, has + n_reads);
+        hv.resize((size_t)n_reads + 8, 0);
+        jd.has = sc::upload(w.passthrough, w.b_has, hv, w.st);
+        return jd;
+    }
+    const JobDev* publish(Worker& w) {
+        const JobDev* jd_dev = (const JobDev*)w.b_jobdev.ensure(sizeof(JobBlock));
+        HIPCHK(hipMemcpyAsync((void*)jd_dev, &jd, sizeof jd, hipMemcpyHostToDevice, w.st));
+        return jd_dev;
+    }
+};
+
 struct sc_ctx { Ctx c; sc_ctx(int device, const CtxPlan& plan) : c(device, plan) {} };
 
 extern "C" {
@@ -295,33 +338,24 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
     try {
         Worker w;                                      // a private worker: own stream, own parameter / result blocks
         w.init_private(ctx);
-        // entries [0, e0) belong to other levels: they name other reads (the last ones, backwards), so that an entry index
-        // that misses e0 reads the wrong row
         const int E = e0 + n_ent;
-        FlatGraph f;
+        LevelStub stub;
+        FlatGraph& f = stub.f;
         f.K = KMAX; f.code_N = KMAX;
-        f.ent_rid.resize((size_t)E); f.ent_cn.assign((size_t)E, 1); f.ent_lab_off.resize((size_t)E); f.ent_lab_len.assign((size_t)E, 1);
-        f.ent_first.assign((size_t)E, 1);
-        f.labels.assign((size_t)E + 1, 0);             // [E]: the strains' node label (read only by the update, which does not run)
-        std::vector<int> qoff((size_t)E, 0);
-        for (int e = 0; e < E; e++) {
-            const int r = e - e0;
-            f.ent_rid[(size_t)e] = r >= 0 ? ent_rid[r] : n_reads - 1 - e % n_reads;
-            f.ent_lab_off[(size_t)e] = e;
-            f.labels[(size_t)e] = (uint8_t)(r >= 0 ? ent_sym[r] : 0);
+        stub.entries(e0, n_ent, n_reads, (size_t)E + 1);      // labels[E]: the strains' node label (read only by the update, which does not run)
+        for (int r = 0, q = 0; r < n_ent; r++) {
+            const size_t e = (size_t)(e0 + r);
+            f.ent_rid[e] = ent_rid[r]; f.labels[e] = (uint8_t)ent_sym[r]; f.ent_cn[e] = ent_cn[r];
+            stub.qoff[e] = q; q += ent_cn[r];
         }
-        for (int r = 0, q = 0; r < n_ent; r++) { f.ent_cn[(size_t)(e0 + r)] = ent_cn[r]; qoff[(size_t)(e0 + r)] = q; q += ent_cn[r]; }
+        stub.mptr.assign(mate_off, mate_off + n_reads + 1);
+        if (nm > 0) stub.midx.assign(mate_idx, mate_idx + nm);
         const hipStream_t st = w.st;
-        const std::vector<int> mptr(mate_off, mate_off + n_reads + 1), midx(mate_idx, mate_idx + nm);      // (alive until the copies are done)
-        JobDev jd = w.job_dev(w.passthrough, f, qoff, mptr, midx, n_reads, std::max<long>(Q, 1), n_ent, Q * n_sweeps);
         // rows as in the region set-up; strain s lives in row slot(s), not in row s
         auto slot = [](int s) { return (s * 37 + 5) % MAXS; };
-        std::vector<double> rows((size_t)jd.ll_stride * MAXS, 0.0);
-        for (int s = 0; s < S; s++) std::memcpy(&rows[(size_t)slot(s) * jd.ll_stride], ll + (size_t)s * n_reads, sizeof(double) * n_reads);
-        jd.ll = upload(w.passthrough, w.b_ll, rows, st);
-        std::vector<uint8_t> hv(has, has + n_reads);
-        hv.resize((size_t)n_reads + 8, 0);
-        jd.has = upload(w.passthrough, w.b_has, hv, st);
+        std::vector<int> slots((size_t)S);
+        for (int s = 0; s < S; s++) slots[(size_t)s] = slot(s);
+        JobDev& jd = stub.upload(w, n_reads, std::max<long>(Q, 1), n_ent, Q * n_sweeps, S, slots.data(), ll, has);
         // the uniforms, padded by 2048 values as the context pads its stream (the chain stages windows of 1024)
         std::vector<double> u(U, U + Q * n_sweeps);
         u.resize((size_t)(Q * n_sweeps + 2048), 0.5);
@@ -329,8 +363,7 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         DevBuf b_u, b_uf;
         jd.U = upload(w.passthrough, b_u, u, st);
         jd.Uf = upload(w.passthrough, b_uf, uf, st);
-        const JobDev* jd_dev = (const JobDev*)w.b_jobdev.ensure(sizeof(JobBlock));
-        HIPCHK(hipMemcpyAsync((void*)jd_dev, &jd, sizeof jd, hipMemcpyHostToDevice, st));
+        const JobDev* jd_dev = stub.publish(w);
 
         LevelParams& P = *w.Ph;
         for (int s = 0; s < S; s++) {
@@ -352,6 +385,108 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         for (int s = 0; s < S; s++) kdraw[s] = R.kdraw[s];
         std::memcpy(cnt, R.cnt, sizeof(unsigned) * (size_t)S * KMAX);
         out[0] = (long)R.n_draws; out[1] = (long)R.n_slow; out[2] = (long)R.n_exact; out[3] = (long)R.n_pass; out[4] = kind; out[5] = done;
+        return SC_OK;
+    } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
+    catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
+}
+int sc_update_level(sc_ctx* h, int S, const int* slot, const int* lab_off, const int* lab_len, int K, int code_N, const double* lpt,
+                    int n_reads, const double* ll, const unsigned char* has, const unsigned char* labels, int n_labels, int n_ent,
+                    int e0, const int* ent_rid, const int* ent_lab_off, const int* ent_lab_len, const unsigned char* ent_first,
+                    int n_copy, const int* copy_src, const int* copy_dst, int copy_n, double* ll_out, unsigned char* has_out,
+                    unsigned char* isnew_out, int* done_out) {
+    if (!h || !slot || !lab_off || !lab_len || !lpt || !ll || !has || !labels || !ent_rid || !ent_lab_off || !ent_lab_len || !ent_first ||
+        !ll_out || !has_out || !isnew_out || !done_out)
+        return SC_ERR_ARG;
+    Ctx* ctx = &h->c;
+    if (ctx->resident || ctx->workers.size() != 1) return SC_ERR_ARG;      // as sc_sample_level
+    if (S < 1 || S > MAXS || K < 6 || K > KMAX || !(code_N == -1 || (code_N >= 6 && code_N < K)) || n_reads < 1 ||
+        n_reads > (1 << 16) || n_ent < 1 || n_ent > (1 << 16) || e0 < 0 || e0 > (1 << 20) || n_labels < 1 || n_labels > (1 << 24) || n_copy < 0 || n_copy > MAXS || copy_n < 0)
+        return SC_ERR_ARG;
+    if ((long)S * K * K > (long)level_table_capacity()) return SC_ERR_ARG;
+    if (n_copy > 0 && (!copy_src || !copy_dst)) return SC_ERR_ARG;
+    // Everything a kernel indexes with.  A label lies inside `labels`; one of a single symbol may hold any code (the
+    // single-symbol paths check a < K && b < K themselves); the walks over a multi-symbol label index the strain's table
+    // unchecked, so every code they meet is below K (an N of the strain's label becomes the read's symbol first): the codes
+    // of every multi-symbol label, and of every entry's label once a strain's label has more than one symbol.
+    auto label_ok = [&](int off, int len, bool strain, bool walked) {
+        if (len < 1 || off < 0 || (long)off + len > (long)n_labels) return false;
+        if (len == 1 && !walked) return true;
+        for (int i = 0; i < len; i++) {
+            const int c = labels[off + i];
+            if (!(c < K || (strain && c == code_N))) return false;
+        }
+        return true;
+    };
+    bool multi_strain = false;
+    uint64_t taken[2] = {0, 0}, dst_rows[2] = {0, 0}, src_rows[2] = {0, 0};
+    auto bit = [](const uint64_t* m, int r) { return (m[r >> 6] >> (r & 63)) & 1; };
+    auto set = [](uint64_t* m, int r) { m[r >> 6] |= 1ull << (r & 63); };
+    for (int s = 0; s < S; s++) {
+        if (slot[s] < 0 || slot[s] >= MAXS || bit(taken, slot[s])) return SC_ERR_ARG;
+        set(taken, slot[s]);
+        if (!label_ok(lab_off[s], lab_len[s], true, lab_len[s] > 1)) return SC_ERR_ARG;
+        if (lab_len[s] > 1) multi_strain = true;
+    }
+    bool has_dups = false, any_multi = multi_strain;
+    for (int r = 0; r < n_ent; r++) {
+        if (ent_rid[r] < 0 || ent_rid[r] >= n_reads || !label_ok(ent_lab_off[r], ent_lab_len[r], false, multi_strain)) return SC_ERR_ARG;
+        if (!ent_first[r]) has_dups = true;                 // as LevelWalk::run derives them from the level's entries
+        if (ent_lab_len[r] != 1) any_multi = true;
+    }
+    // the copies are independent: a destination is no other pair's destination and nobody's source
+    for (int c = 0; c < n_copy; c++) {
+        if (copy_src[c] < 0 || copy_src[c] >= MAXS || copy_dst[c] < 0 || copy_dst[c] >= MAXS || bit(dst_rows, copy_dst[c])) return SC_ERR_ARG;
+        set(dst_rows, copy_dst[c]); set(src_rows, copy_src[c]);
+    }
+    if ((dst_rows[0] & src_rows[0]) || (dst_rows[1] & src_rows[1])) return SC_ERR_ARG;
+    try {
+        Worker w;                                      // a private worker: own stream, own parameter / result blocks
+        w.init_private(ctx);
+        const int E = e0 + n_ent;
+        LevelStub stub;
+        FlatGraph& f = stub.f;
+        f.K = K; f.code_N = code_N;
+        stub.entries(e0, n_ent, n_reads, (size_t)e0 + (size_t)n_labels);      // the caller's labels behind those of the entries in front
+        std::memcpy(f.labels.data() + e0, labels, (size_t)n_labels);
+        for (int r = 0; r < n_ent; r++) {
+            const size_t e = (size_t)(e0 + r);
+            f.ent_rid[e] = ent_rid[r]; f.ent_lab_off[e] = e0 + ent_lab_off[r]; f.ent_lab_len[e] = ent_lab_len[r];
+            f.ent_first[e] = ent_first[r] ? 1 : 0;
+            stub.qoff[e] = r;
+        }
+        const hipStream_t st = w.st;
+        const JobDev& jd = stub.upload(w, n_reads, n_ent, n_ent, 1, S, slot, ll, has);
+        const JobDev* jd_dev = stub.publish(w);
+
+        // the level's parameters as LevelWalk::run_level states them
+        LevelParams& P = *w.Ph;
+        for (int s = 0; s < S; s++) {
+            P.sp[s] = StrainParam{slot[s], e0 + lab_off[s], lab_len[s], 0, 1.0, 0.0};
+            w.gp.slot[s] = (uint8_t)slot[s];
+            w.gp.lab[s] = f.labels[(size_t)(e0 + lab_off[s])];
+        }
+        for (int c = 0; c < n_copy; c++) {
+            P.copy_src[c] = copy_src[c]; P.copy_dst[c] = copy_dst[c];
+            w.gp.copy_src[c] = (uint8_t)copy_src[c]; w.gp.copy_dst[c] = (uint8_t)copy_dst[c];
+        }
+        std::memcpy(P.lpt, lpt, sizeof(double) * (size_t)S * K * K);             // compact [K][K]
+        LevelHdr H{};
+        H.mode = MODE_SAMPLE; H.S = S; H.e0 = e0; H.e1 = E; H.has_dups = has_dups; H.any_multi = any_multi; H.Q = n_ent;
+        H.n_sweeps = 0;                                // no sampler: level_kind gives 0, level_plain_body returns behind the update
+        H.n_copy = n_copy; H.copy_n = copy_n; H.do_update = 1; H.seq = 1;
+        std::memset(w.Rh, 0, sizeof(LevelResult));
+        const LevelItem it = w.level_item(jd_dev, H, K);
+        if (item_kind(it.kind) != 0) throw ScError(SC_ERR_INTERNAL, "a level without sweeps asked for the sampler");
+        const int done = launch_level(st, it, w.gp, w.hp, n_reads);      // as the walk of a single region launches its levels
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        if (w.Rh->seq != 1u || w.Rh->error) throw ScError(SC_ERR_INTERNAL, "the level did not complete");
+        std::vector<double>& rows = stub.rows;         // the whole matrix back, without the padding of its stride
+        HIPCHK(hipMemcpy(rows.data(), jd.ll, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+        for (int r = 0; r < MAXS; r++) std::memcpy(ll_out + (size_t)r * n_reads, &rows[(size_t)r * jd.ll_stride], sizeof(double) * (size_t)n_reads);
+        HIPCHK(hipMemcpy(has_out, jd.has, (size_t)n_reads, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(isnew_out, jd.isnew, (size_t)n_ent, hipMemcpyDeviceToHost));
+        *done_out = done;
         return SC_OK;
     } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
     catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }

@@ -12,9 +12,9 @@ sc_sample_level runs a level without an update (the read_assign shape).  What on
 symbols and log tables of k_level_update, the copies of k_level_copy, the marks between the update and the rows --
 is reached by whole regions (seeds 2 and 7 of make_case, and a paired region without indels made here), wide against
 narrow, with the level log showing which pieces ran on the grid and with how many copies.  The log names counts, not
-values: test_copy_counts_and_mates_on_levels_with_an_update lists the cases of an update that no entry point of the
-library can express (a label N, K = 5, a symbol >= K, K = KMAX) and why.  Step 3 of the work (fewer launches) was not
-built: k_level_entries is launched as before."""
+values: the values of an update and of its copies (a label N, a symbol >= K, K = KMAX, which pairs a level copies) are
+compared on single levels through sc_update_level (tests/test_update_edges_gpu.py).  Step 3 of the work (fewer launches)
+was not built: k_level_entries is launched as before."""
 import json
 import os
 import pickle
@@ -297,16 +297,10 @@ def test_copy_counts_and_mates_on_levels_with_an_update(update_runs):
     the rows of those levels read `has` of mates that the marks in front of them set or left).  The FASTA is the oracle's
     and the %.17g trace the narrow run's, byte for byte.
 
-    What the entry points cannot express, and what therefore has no case here (a decision, not an oversight):
-    * which pairs a level copies and which of the four (hr, hu) combinations its slots take -- the level log names counts
-      only; the four combinations and the same-level mate are asserted on the single level `mates` above, which has no
-      update;
-    * a strain label N (`g.lab == code_N`, the diagonal): reads with an N at a site where seven in ten carry it give no
-      candidate with an N in the oracle's trace or in this library's -- the letter does not reach a node label;
-    * K = 5 and a symbol >= K (the NaN cell): the walk's alphabet starts with its six fixed symbols and numbers what it
-      finds 0 .. K - 1; sc_sample_level sets K = KMAX and code_N = KMAX but runs no update;
-    * K = KMAX: the oracle does not finish a region whose reads carry the nine IUPAC letters within two minutes, so there is
-      no reference to compare with."""
+    What the entry points cannot express, and what therefore has no case here (a decision, not an oversight): which of the
+    four (hr, hu) combinations a region's slots take -- the level log names counts only; the four combinations and the
+    same-level mate are asserted on the single level `mates` above, which has no update.  (A strain label N, a symbol >= K,
+    K = KMAX and which pairs a level copies are cases of tests/update_edge_lib.py, through sc_update_level.)"""
     exp_fa, (w_fa, w_trace, w_log), (n_fa, n_trace, n_log) = update_runs
     summary = [(int(r["S"]), int(r["ncopy"]), int(r["copyn"]), int(r["multi"]), int(r["done"]), float(r["chain_us"]) > 0) for r in w_log]
     print("S ncopy copyn multi done sampler:", summary)
