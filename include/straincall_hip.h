@@ -210,7 +210,7 @@ int sc_update_level(sc_ctx* ctx, int S, const int* slot, const int* lab_off, con
                     const unsigned char* ent_first, int n_copy, const int* copy_src, const int* copy_dst, int copy_n,
                     double* ll_out, unsigned char* has_out, unsigned char* isnew_out, int* done_out);
 
-/* ---- rows a2-a4 on the host: the alignment file and a window's reads (rambl_amd/csrc/sc_ingest.cpp) ----------
+/* ---- rows a2-a4 on the host: the alignment file and a window's reads (rambl_amd/csrc/sc_aln_file.cpp, sc_ingest.cpp) ----------
  *
  * The reference shells out to samtools for every window (StrainCall.cpp:496 `view -q mq -F 1804 region`, :696
  * `mpileup -q mq -Q0 -A -r region`) and parses the text.  Here the file (SAM text, or BAM read natively: BGZF +

@@ -24,11 +24,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/straincall_hip.h"
 #include "sc_host.hpp"
+#include "sc_cigar.hpp"
 #include "sc_ingest.hpp"
 
 namespace {
@@ -208,20 +208,6 @@ __global__ __launch_bounds__(256) void k_depth_fused(const uint2* __restrict__ r
     }
 }
 
-int host_threads() {
-    long quota = 0;
-    if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-        long q = 0, per = 0;
-        if (fscanf(f, "%ld %ld", &q, &per) == 2 && q > 0 && per > 0) quota = (q + per - 1) / per;
-        fclose(f);
-    }
-    long n = (long)std::thread::hardware_concurrency();
-    if (quota > 0 && quota < n) n = quota;
-    if (const char* e = getenv("LOCAL_WORLD_SIZE")) { const long k = atol(e); if (k > 1) n = std::max<long>(n / k, 1); }
-    if (const char* e = getenv("SC_INGEST_THREADS")) n = atol(e);
-    return (int)std::min<long>(std::max<long>(n, 1), 32);
-}
-
 // The device part: runs bucketed by reference (run_ptr[n_refs + 1]), 0-based inclusive (start, end) pairs; the runs of a
 // reference longer than a tile sorted by start.  `runs` is page-locked.  A failed HIP call throws sc::HipError.
 int depth_scan_bucketed(const int* ref_len, int n_refs, const unsigned* run_ptr, const uint2* runs, long n_runs, int max_run, int max_gap,
@@ -351,44 +337,30 @@ int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const
     // rank take them in turns (the CIGAR walk of 10^7 records is the longest part of the stage once the device needs 0.1 ms)
     const double t0 = sc::now_ms();
     std::vector<std::vector<uint2>> per_ref((size_t)n_refs);
-    std::atomic<int> next{0};
     std::atomic<int> max_run_all{1};
-    auto work = [&]() {
+    sc::parallel_items(n_refs, std::max(1, std::min(sc::ingest_threads(), n_refs / 64 + 1)), [&](int r) {
         int max_run = 1;
-        for (int r = next.fetch_add(1); r < n_refs; r = next.fetch_add(1)) {
-            std::vector<uint2>& out = per_ref[(size_t)r];
-            for (int f = 0; f < n_alns; f++) {
-                auto it = alns[f]->by_ref.find(ref_names[r]);
-                if (it == alns[f]->by_ref.end()) continue;
-                for (const sc_ingest::Rec& rec : it->second) {
-                    if (rec.flag & 0x704) continue;                      // samtools depth: unmapped, secondary, QC fail, duplicate
-                    long v = 0;
-                    int p = rec.pos;
-                    for (int i = 0; i < rec.clen; i++) {
-                        const char ch = rec.cigar[i];
-                        if (ch >= '0' && ch <= '9') { v = v * 10 + (ch - '0'); continue; }
-                        if (ch == 'M' || ch == '=' || ch == 'X') {
-                            const int a = std::max(p, 1), b = std::min(p + (int)v - 1, ref_len[r]);
-                            if (a <= b) { out.push_back(make_uint2((unsigned)(a - 1), (unsigned)(b - 1))); max_run = std::max(max_run, b - a + 1); }
-                            p += (int)v;
-                        } else if (ch == 'D' || ch == 'N') {
-                            p += (int)v;                                  // a deleted / skipped base is no depth
-                        }
-                        v = 0;
+        std::vector<uint2>& out = per_ref[(size_t)r];
+        for (int f = 0; f < n_alns; f++) {
+            auto it = alns[f]->by_ref.find(ref_names[r]);
+            if (it == alns[f]->by_ref.end()) continue;
+            for (const sc_ingest::Rec& rec : it->second) {
+                if (rec.flag & 0x704) continue;                      // samtools depth: unmapped, secondary, QC fail, duplicate
+                int p = rec.pos;
+                sc_ingest::for_each_op(rec.cigar, rec.clen, [&](char op, long len) {
+                    if (op == 'M' || op == '=' || op == 'X') {
+                        const int a = std::max(p, 1), b = std::min(p + (int)len - 1, ref_len[r]);
+                        if (a <= b) { out.push_back(make_uint2((unsigned)(a - 1), (unsigned)(b - 1))); max_run = std::max(max_run, b - a + 1); }
+                        p += (int)len;
+                    } else if (op == 'D' || op == 'N') {
+                        p += (int)len;                                // a deleted / skipped base is no depth
                     }
-                }
+                });
             }
         }
         int m = max_run_all.load();
         while (max_run > m && !max_run_all.compare_exchange_weak(m, max_run)) {}
-    };
-    {
-        const int nt = std::max(1, std::min(host_threads(), n_refs / 64 + 1));
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; t++) pool.emplace_back(work);
-        work();
-        for (auto& th : pool) th.join();
-    }
+    });
     if (stats) stats->extract_ms = sc::now_ms() - t0;
     const double t1 = sc::now_ms();
     std::vector<unsigned> ptr((size_t)n_refs + 1, 0);

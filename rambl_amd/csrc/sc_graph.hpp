@@ -8,14 +8,13 @@
 // clustering kernels consume (sc_flatten.cpp; the kernels: sc_graph_kernels.hip).
 // The insertion MSA (row a7) is delegated to the device through `MsaFn`.
 #pragma once
-#include <atomic>
 #include <cstdint>
 #include <functional>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 #include "sc_std_sort.hpp"
+#include "sc_threads.hpp"       // parallel_items
 
 namespace sc {
 
@@ -130,27 +129,6 @@ private:
 // worker that builds the graph.
 void set_graph_threads(int n, long min_entries = 1L << 22);
 int graph_threads(long entries);       // threads for a bulk copy of that many pool entries
-
-// fn(i, scratch) for i in [0, n), on up to `threads` threads taking indices from a shared counter (the items differ in size
-// by orders of magnitude: a backbone class of 59 000 reads beside a sibling of three); every thread makes a scratch of its
-// own with scratch().  On one thread the items run in order.  Exceptions of a helper end the process as they would on the
-// calling thread.
-template <class S, class F>
-void parallel_items(int n, int threads, const S& scratch, const F& fn) {
-    std::atomic<int> next{0};
-    auto body = [&] {
-        auto s = scratch();
-        for (int i = next.fetch_add(1, std::memory_order_relaxed); i < n; i = next.fetch_add(1, std::memory_order_relaxed)) fn(i, s);
-    };
-    std::vector<std::thread> ts;
-    for (int t = 1; t < threads && n >= 2; t++) ts.emplace_back(body);
-    body();
-    for (auto& t : ts) t.join();
-}
-template <class F>
-void parallel_items(int n, int threads, const F& fn) {
-    parallel_items(n, threads, [] { return 0; }, [&](int i, int&) { fn(i); });
-}
 
 // ---------------------------------------------------------------------------
 // Level-major flattening for the device (sc_flatten.cpp).

@@ -16,34 +16,39 @@
 
 namespace sc {
 
-// mt19937(1234) -> generate_canonical<double,53>: the stream every sampler call
-// of the reference starts from (NonparametricClustering.cpp:142,785)
-inline std::vector<double> uniform_stream(unsigned seed, int n) {
-    std::vector<uint32_t> x(624);
-    x[0] = seed;
-    for (int i = 1; i < 624; i++) x[i] = 1812433253u * (x[i - 1] ^ (x[i - 1] >> 30)) + (uint32_t)i;
-    int p = 624;
-    auto next = [&]() -> uint32_t {
+// std::mt19937 + std::generate_canonical<double,53> as libstdc++ has them
+struct Mt19937 {
+    uint32_t x[624]; int p = 624;
+    explicit Mt19937(uint32_t seed) {
+        x[0] = seed;
+        for (int i = 1; i < 624; i++) x[i] = 1812433253u * (x[i - 1] ^ (x[i - 1] >> 30)) + (uint32_t)i;
+    }
+    uint32_t next() {
         if (p >= 624) {
-            const uint32_t UP = 0x80000000u, LO = 0x7fffffffu;
-            for (int k = 0; k < 624 - 397; ++k) { uint32_t y = (x[k] & UP) | (x[k + 1] & LO); x[k] = x[k + 397] ^ (y >> 1) ^ ((y & 1) ? 0x9908b0dfu : 0); }
-            for (int k = 624 - 397; k < 623; ++k) { uint32_t y = (x[k] & UP) | (x[k + 1] & LO); x[k] = x[k + (397 - 624)] ^ (y >> 1) ^ ((y & 1) ? 0x9908b0dfu : 0); }
-            uint32_t y = (x[623] & UP) | (x[0] & LO);
-            x[623] = x[396] ^ (y >> 1) ^ ((y & 1) ? 0x9908b0dfu : 0);
+            auto twist = [this](int k, int k1, int km) {
+                const uint32_t y = (x[k] & 0x80000000u) | (x[k1] & 0x7fffffffu);
+                x[k] = x[km] ^ (y >> 1) ^ ((y & 1) ? 0x9908b0dfu : 0);
+            };
+            for (int k = 0; k < 624 - 397; ++k) twist(k, k + 1, k + 397);
+            for (int k = 624 - 397; k < 623; ++k) twist(k, k + 1, k + (397 - 624));
+            twist(623, 0, 396);
             p = 0;
         }
         uint32_t z = x[p++];
         z ^= (z >> 11); z ^= (z << 7) & 0x9d2c5680u; z ^= (z << 15) & 0xefc60000u; z ^= (z >> 18);
         return z;
-    };
-    std::vector<double> u(n);
-    for (int i = 0; i < n; i++) {
-        double sum = 0.0, tmp = 1.0;
-        for (int k = 2; k != 0; --k) { sum += (double)next() * tmp; tmp *= 4294967296.0; }
-        double r = sum / tmp;
-        if (r >= 1.0) r = std::nextafter(1.0, 0.0);
-        u[i] = r;
     }
+    double canonical() {
+        const double lo = (double)next(), hi = (double)next();
+        const double r = (lo + hi * 4294967296.0) / 18446744073709551616.0;
+        return r >= 1.0 ? 0x1.fffffffffffffp-1 : r;
+    }
+};
+// mt19937(1234) -> generate_canonical<double,53>: the stream every sampler call of the reference starts from (NonparametricClustering.cpp:142,785)
+inline std::vector<double> uniform_stream(unsigned seed, int n) {
+    Mt19937 gen(seed);
+    std::vector<double> u(n);
+    for (double& v : u) v = gen.canonical();
     return u;
 }
 

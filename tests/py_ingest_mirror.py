@@ -1,7 +1,7 @@
 """Second implementation of the host ingest (rows a2-a4), in Python -- TEST INFRASTRUCTURE.
 
-The product reads alignment files and ingests windows in C++ (rambl_amd/csrc/sc_ingest.cpp: sc_aln_*).  This module is the
-independent restatement the tests compare it with: the records of a SAM text / BAM file as Python objects, `samtools view`
+The product reads alignment files and ingests windows in C++ (rambl_amd/csrc/sc_aln_file.cpp, sc_ingest.cpp: sc_aln_*).  This
+module is the independent restatement the tests compare it with: the records of a SAM text / BAM file as Python objects, `samtools view`
 and `samtools mpileup` emulated as TEXT (what /root/reference/StrainCall/StrainCall.cpp:496,696 parses), the pileup summary
 read from that text as window_adjust reads it (:702-736), and load_mapping_reads (:480-670) with crop_read_within_window
 (:291-414), read_align_end_pos (:276-289), max_insert_size (:427-440), parse_cigar (PartialOrderGraph.cpp:13-59) and
@@ -98,7 +98,7 @@ def crop_read_within_window(w0, w1, seq, qual, ops, r0, r1):
     away along a reference coordinate map of the operations: M and D are clipped position by position, an insertion
     in front of the first / behind the last kept reference position leaves with its bases, operations the reference
     does not know to consume anything (N, H, P) stay as they are.  Same rules as `crop_to_window` in
-    rambl_amd/csrc/sc_ingest.cpp (the product's reader); raises where the C++ of the reference would run past a vector
+    rambl_amd/csrc/sc_cigar.hpp (the product's reader); raises where the C++ of the reference would run past a vector
     or a string."""
     n = len(ops)
     lead = trail = 0

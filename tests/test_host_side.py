@@ -5,6 +5,7 @@ import ctypes
 import io
 import os
 import random
+import re
 import subprocess
 
 import numpy as np
@@ -235,6 +236,162 @@ def test_crop_and_cigar_helpers():
     assert mirror.crop_read_within_window(5, 8, "ACGTACGTAC", "IIIIIIIIII", cig, 3, 12) == ("GTAC", "4M")
     assert mirror.crop_read_within_window(1, 100, "ACGTACGTAC", "IIIIIIIIII", cig, 3, 12) == ("ACGTACGTAC", "10M")
     assert mirror.max_insert_size("5M3I2M7I1M") == 7
+
+
+@pytest.fixture(scope="module")
+def ingest_check_bin(tmp_path_factory):
+    """tests/native/ingest_check.cpp with the two ingest sources, plain g++ under the address and undefined-behaviour
+    sanitizers: not the library, nothing loaded into Python."""
+    out = str(tmp_path_factory.mktemp("native") / "ingest_check")
+    csrc = os.path.join(ROOT, "rambl_amd", "csrc")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-o", out, os.path.join(ROOT, "tests", "native", "ingest_check.cpp"), os.path.join(csrc, "sc_aln_file.cpp"),
+                           os.path.join(csrc, "sc_ingest.cpp"), "-lz", "-lpthread"])
+    return out
+
+
+def _crop_named_cases():
+    """(name, w0, w1, pos, cigar) at the smallest sizes.  The plain reads cover 10-19 (10M), 10-14 + 15-19 around an
+    insertion (5M2I5M), 10-14 + 17-21 around a deletion at 15-16 (5M2D5M)."""
+    plain = [
+        ("window starts inside an M", 12, 30, 10, "10M"),
+        ("window starts inside a D", 16, 30, 10, "5M2D5M"),
+        ("window starts on the M/I boundary, insertion in front of w0", 15, 30, 10, "5M2I5M"),
+        ("window starts on the last M base before the I", 14, 30, 10, "5M2I5M"),
+        ("window starts on the M/D boundary", 15, 30, 10, "5M2D5M"),
+        ("window starts on the first M base after the D", 17, 30, 10, "5M2D5M"),
+        ("insertion immediately after w1", 5, 14, 10, "5M2I5M"),
+        ("window ends on the first M base after the I", 5, 15, 10, "5M2I5M"),
+        ("window ends on the M/D boundary", 5, 14, 10, "5M2D5M"),
+        ("window ends inside the D", 5, 15, 10, "5M2D5M"),
+        ("read ends exactly at w1", 5, 19, 10, "10M"),
+        ("read ends one past w1", 5, 18, 10, "10M"),
+        ("read starts exactly at w0", 10, 30, 10, "10M"),
+        ("read starts one before w0", 11, 30, 10, "10M"),
+        ("read wholly inside the window", 5, 30, 10, "10M"),
+        ("read covers the whole window", 12, 15, 10, "10M"),
+        ("w0 == w1 inside the read", 12, 12, 10, "10M"),
+        ("w0 == w1 on the read's first base", 10, 10, 10, "10M"),
+        ("w0 == w1 on the read's last base", 19, 19, 10, "10M"),
+        ("w0 == w1 inside a D", 15, 15, 10, "5M2D5M"),
+        ("N inside the window", 5, 30, 10, "4M3N4M"),
+        ("N across the window start", 15, 30, 10, "4M3N4M"),
+        ("N across the window end", 5, 15, 10, "4M3N4M"),
+        ("= and X", 5, 30, 3, "3=1X2I1D2M"),
+        ("= and X cut at both ends", 4, 7, 3, "3=1X2I1D2M"),
+        ("zero-length operation first", 5, 30, 10, "0M10M"),
+        ("zero-length operation first, cut in front", 12, 30, 10, "0M10M"),
+        ("read wholly before the window", 30, 40, 10, "10M"),
+        ("read wholly after the window", 30, 40, 50, "10M"),
+        ("everything consumed by the front walk", 20, 30, 10, "10M"),
+    ]
+    cases = list(plain)
+    cases += [(name + ", soft clips on both ends", w0, w1, pos, "3S" + cig + "4S") for name, w0, w1, pos, cig in plain]
+    cases += [
+        ("H outside the S", 12, 17, 10, "2H3S10M4S2H"),
+        ("H outside the S, read inside the window", 5, 30, 10, "2H3S10M4S2H"),
+        ("zero-length soft clip first", 12, 30, 10, "0S10M"),
+        ("only S", 5, 30, 10, "5S"),
+        ("only S and H", 5, 30, 10, "5S2H"),
+        ("trailing S when the front walk consumed everything else", 20, 30, 10, "10M4S"),
+        ("trailing S after an insertion the back walk removes", 5, 14, 10, "5M2I5M4S"),
+    ]
+    return cases
+
+
+def _crop_random_cases(seed=7, n=2000):
+    """CIGARs and positions of _random_sam's generator, each with a window that starts near the read's start."""
+    import tempfile
+    rng = random.Random(seed)
+    with tempfile.TemporaryDirectory() as d:
+        _random_sam(rng, os.path.join(d, "x.sam"), n=n)
+        recs = [ln.split("\t") for ln in open(os.path.join(d, "x.sam")) if not ln.startswith("@")][:n]
+    cases = []
+    for k, f in enumerate(recs):
+        w0 = max(1, int(f[3]) + rng.randint(-20, 30))
+        cases.append(("random %d" % k, w0, w0 + rng.randint(0, 120), int(f[3]), f[5]))
+    return cases
+
+
+def _bam_error_files(d):
+    """{file: the message sc_aln_open must give}: BGZF and BAM bytes broken by hand in one place each, and the intact file."""
+    import struct
+    head = b"BAM\x01" + struct.pack("<i", 0) + struct.pack("<i", 1) + struct.pack("<i", 2) + b"g\x00" + struct.pack("<i", 50)
+
+    def rec(l_seq, extra_block=0):
+        body = struct.pack("<iiBBHHHiiii", 0, 4, 3, 30, 4680, 1, 0, l_seq, -1, -1, 0) + b"r1\x00" + struct.pack("<I", 4 << 4) + bytes([0x12, 0x48]) + bytes([30] * 4)
+        return struct.pack("<i", len(body) + extra_block) + body
+
+    good = _bgzf_block(head + rec(4))
+    no_bc = good.replace(b"BC", b"XY", 1)
+    big = good[:-4] + struct.pack("<I", 65537)
+    crc = good[:-8] + struct.pack("<I", struct.unpack("<I", good[-8:-4])[0] ^ 1) + good[-4:]
+    files = {
+        "good.bam": (good, ""),
+        "cut_in_data.bam": (good[:-10], "BGZF block without a BC field or truncated"),
+        "cut_in_extra.bam": (good[:20], "truncated BGZF block"),
+        "no_bc.bam": (no_bc, "BGZF block without a BC field or truncated"),
+        "isize.bam": (big, "BGZF block claims more than 64 KiB of data"),
+        "crc.bam": (crc, "corrupt BGZF block (inflate or CRC-32)"),
+        "block_size.bam": (_bgzf_block(head + rec(4, extra_block=100)), "truncated BAM record"),
+        "l_seq.bam": (_bgzf_block(head + rec(4000)), "corrupt BAM record"),
+        "l_seq_negative.bam": (_bgzf_block(head + rec(-1)), "corrupt BAM record"),
+    }
+    for name, (blob, _) in files.items():
+        open(os.path.join(d, name), "wb").write(blob)
+    return {os.path.join(d, name): msg for name, (_, msg) in files.items()}
+
+
+def test_ingest_native_check(ingest_check_bin, tmp_path):
+    """The pure parts of the ingest (sc_cigar.hpp, stable_sort_mt and name_cmp of sc_ingest.hpp, the BGZF/BAM decoder of
+    sc_aln_file.cpp) in a stand-alone program under the host sanitizers, which end the program at the first fault.
+    (a) parse_cigar + crop_to_window on named edge cases and 2 000 random ones equal the Python mirror's
+    crop_read_within_window: bases, CIGAR text, and a failure exactly where the mirror raises.  (b) stable_sort_mt equals
+    std::stable_sort on keys full of ties around every nt * min_stretch; name_cmp orders as std::string does.  (c) every
+    BGZF / BAM error path on hand-made bytes returns its message."""
+    def run(args, text=b""):
+        p = subprocess.run([ingest_check_bin] + args, input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        assert p.returncode == 0, (p.stdout.decode()[-2000:], p.stderr.decode()[-4000:])
+        return p.stdout.decode().split("\n")[:-1]
+    # (a)
+    named, rand = _crop_named_cases(), _crop_random_cases()
+    assert len({c[0] for c in named}) == len(named) and len(rand) == 2000
+    rng = random.Random(11)
+    seqs, want = [], []
+    for name, w0, w1, pos, cig in named + rand:
+        ops = mirror.parse_cigar(cig)
+        seq = "".join(rng.choice("ACGT") for _ in range(sum(int(n) for n in re.findall(r"(\d+)[MIS=X]", cig))))
+        seqs.append(seq)
+        try:
+            want.append(mirror.crop_read_within_window(w0, w1, seq, "I" * len(seq), ops, pos, mirror.read_align_end_pos(pos, ops)))
+        except (IndexError, ValueError):
+            want.append(None)
+    n_fail_random = sum(w is None for w in want[len(named):])
+    assert n_fail_random <= 200, n_fail_random
+    fails = {c[0] for c, w in zip(named, want) if w is None}
+    assert {"only S", "read wholly before the window", "read wholly after the window"} <= fails
+    text = "".join("%d %d %d %s %d\n" % (w0, w1, pos, cig, len(seq)) for (_, w0, w1, pos, cig), seq in zip(named + rand, seqs))
+    out = run(["crop"], text.encode())
+    assert len(out) == len(want)
+    for (name, w0, w1, pos, cig), seq, w, line in zip(named + rand, seqs, want, out):
+        if w is None:
+            assert line == "FAIL", (name, w0, w1, pos, cig, line)
+            continue
+        assert line != "FAIL", (name, w0, w1, pos, cig)
+        lead, trail, got_cig = line.split(" ")
+        bases, exp_cig = w
+        cnt = len(seq) - int(lead) - int(trail)
+        assert (seq[int(lead):] if cnt < 0 else seq[int(lead):int(lead) + cnt], got_cig) == (bases, exp_cig), (name, w0, w1, pos, cig, line)
+    # (b)
+    assert run(["order"])[-1] == "order ok"
+    # (c)
+    files = _bam_error_files(str(tmp_path))
+    out = run(["open"] + list(files))
+    assert len(out) == len(files)
+    for (path, msg), line in zip(files.items(), out):
+        rc, n, got = line.split(" ", 2)
+        assert (rc == "0", got) == (msg == "", msg), (path, line)
+        assert n == ("1" if msg == "" else "0"), (path, line)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 5, 6, 13])
