@@ -494,6 +494,39 @@ const char* sc_taxa_error(void);
 /* The word-list position of draw `draw` of trial `trial` for a list of W words (-1 when W < 1); no device is touched. */
 long sc_taxa_draw(unsigned long long seed, unsigned long long key, int trial, int draw, int W);
 
+/* ---- gene against gene on the device: exact edit distances and the pairs within an identity (rambl_amd/csrc/sc_pairs.hip,
+ * DESIGN.md §8.16) -------------------------------------------------------------------------------------------------------
+ *
+ * The reference has no counterpart that runs (its strain_identity is dead code); the contract is this project's own.
+ *   distance  ed(a, b): the unit-cost edit distance (substitution, insertion, deletion 1 each) of the two whole sequences, no
+ *             free end gaps; A C G T compared in either case, every other byte matches nothing, itself included
+ *   bound     a difference rate is the rational diff_num / diff_den (97 % identity: 3 / 100; 0 <= diff_num <= diff_den);
+ *             bound(a, b) = (max(|a|, |b|) * diff_num) / diff_den in 64-bit integer division; a pair qualifies iff
+ *             ed(a, b) <= bound(a, b).  No floating point takes part.
+ *   gene_text/gene_off[n_genes+1]   the genes back to back, 1..2048 bases each: an empty gene is SC_ERR_ARG, a longer one
+ *             SC_ERR_UNSUPPORTED; the message of the calling thread's last failure is in sc_pairs_error()
+ * sc_gene_distances: dist_out[p] = ed(gene pair_a[p], gene pair_b[p]) for n_pairs arbitrary index pairs (a == b allowed).
+ * sc_gene_pairs: every qualifying pair a < b (indices as the caller numbers the genes) with its distance, sorted by (a, b),
+ * the same on every call; pairs whose lengths differ by more than the bound are never scored.  More than `cap` pairs:
+ * SC_ERR_CAPACITY with *n_pairs set to the number that suffices.
+ * sc_pairs_widths: the words-per-pattern W the kernel is built for, ascending (a pattern of up to 64 W bases runs at the
+ * least listed W that holds it); returns their number and fills the first `cap`.  No device is touched.
+ * stats (may be null) receives the first n_stats of the SC_PAIRS_N_STATS slots below. */
+#define SC_PAIRS_STAT_UPLOAD_MS 0       /* HIP events: genes and tiles to the device */
+#define SC_PAIRS_STAT_KERNEL_MS 1       /* HIP events: k_pairs, every width class */
+#define SC_PAIRS_STAT_TOTAL_MS 2        /* wall time of the call, host packing included */
+#define SC_PAIRS_STAT_TILES 3           /* tiles: a pattern gene with up to 64 text genes */
+#define SC_PAIRS_STAT_PAIRS_SCORED 4    /* pairs that went through the DP */
+#define SC_PAIRS_STAT_PAIRS_SKIPPED 5   /* sc_gene_pairs: pairs a < b left out by their lengths alone */
+#define SC_PAIRS_STAT_WORD_STEPS 6      /* 64-row block steps: text bases * pattern words, summed over the scored pairs */
+#define SC_PAIRS_N_STATS 7
+int sc_gene_distances(int device, const char* gene_text, const long* gene_off, int n_genes, const int* pair_a, const int* pair_b,
+                      long n_pairs, int* dist_out, double* stats, int n_stats);
+int sc_gene_pairs(int device, const char* gene_text, const long* gene_off, int n_genes, int diff_num, int diff_den, int* pair_a,
+                  int* pair_b, int* pair_dist, long cap, long* n_pairs, double* stats, int n_stats);
+int sc_pairs_widths(int* widths, int cap);
+const char* sc_pairs_error(void);
+
 #ifdef __cplusplus
 }
 #endif

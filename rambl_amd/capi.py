@@ -143,6 +143,10 @@ ENTRIES = [
     ("sc_taxa_free", None, [_vp]),
     ("sc_taxa_error", _s, []),
     ("sc_taxa_draw", _l, [_u64, _u64, _i, _i, _i]),
+    ("sc_gene_distances", _i, [_i, _s, _lp, _i, _ip, _ip, _l, _ip, _dp, _i]),
+    ("sc_gene_pairs", _i, [_i, _s, _lp, _i, _i, _i, _ip, _ip, _ip, _l, _lp, _dp, _i]),
+    ("sc_pairs_widths", _i, [_ip, _i]),
+    ("sc_pairs_error", _s, []),
 ]
 EXPORTS = [name for name, _, _ in ENTRIES]
 

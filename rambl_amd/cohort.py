@@ -174,6 +174,9 @@ def main(argv=None):
     ap.add_argument("--ka-k", dest="ka_k", type=float, default=profile.KA_K, help="Karlin-Altschul K [%g]" % profile.KA_K)
     ap.add_argument("--batch-segments", dest="batch_segments", type=int, default=BATCH_SEGMENTS, metavar="N",
                     help="whole samples of at most N segments share a device call; a larger sample goes alone [%d]" % BATCH_SEGMENTS)
+    ap.add_argument("--otu", dest="otu", default=None, metavar="PCT",
+                    help="then cluster the genes into OTUs at this identity in percent, weighted by their matrix rows, and write what "
+                         "`rambl-otu GENE_SEQ --id PCT --matrix %s` writes beside the matrix [off]" % MATRIX_NAME)
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("-v", "--verbose", dest="verbose", action="store_true", help="verbose output")
     a = ap.parse_args(argv)
@@ -194,12 +197,19 @@ def main(argv=None):
         from . import samio
         if not samio.Fasta(a.fasta).order:
             raise ValueError("%s holds no gene" % a.fasta)
+        if a.otu is not None:
+            from . import otu
+            diff = otu.diff_from_identity(a.otu)
+            names, seqs, _ = otu.load_inputs(a.fasta)
     except (ValueError, OSError) as e:
         ap.error(str(e))
     os.environ["SC_INGEST_THREADS"] = str(max(1, min(a.cores, capi.host_plan(1)[2])))
-    cohort_profile(a.fasta, samples, a.out_dir, a.max_align_iden, a.e_value, a.relative_abundance, a.ka_lambda, a.ka_k, a.device, a.seeded,
-                   None if a.copy_correct is None else (a.copy_correct, a.copy_number, 0.6 if a.copy_thresh is None else a.copy_thresh),
-                   a.batch_segments, a.verbose)
+    path, _ = cohort_profile(a.fasta, samples, a.out_dir, a.max_align_iden, a.e_value, a.relative_abundance, a.ka_lambda, a.ka_k, a.device, a.seeded,
+                             None if a.copy_correct is None else (a.copy_correct, a.copy_number, 0.6 if a.copy_thresh is None else a.copy_thresh),
+                             a.batch_segments, a.verbose)
+    if a.otu is not None:
+        with open(path) as f:
+            otu.cluster(names, seqs, diff, f.read(), a.out_dir, False, a.device, a.verbose)
     return 0
 
 
