@@ -166,7 +166,7 @@ __global__ __launch_bounds__(64) void k_sw_trace(const uint8_t* seeds, const lon
     }
 }
 
-thread_local LastError tl_error;
+thread_local sc::LastError tl_error;
 
 }  // namespace
 
@@ -176,109 +176,107 @@ const char* sc_align_error(void) { return tl_error.text.c_str(); }
 
 int sc_align_reads(int device, const char* seed_text, const long* seed_off, int n_seeds, const char* read_text, const char* qual_text,
                    const long* read_off, int n_reads, int* as, int* xs, int* seed, int* strand, int* pos, int* nm, unsigned* cigar,
-                   int cigar_stride, int* n_cigar, sc_align_stats* stats) try {
-    tl_error.text.clear();
+                   int cigar_stride, int* n_cigar, sc_align_stats* stats) {
+    tl_error.clear();
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!seed_text || !seed_off || n_seeds < 1 || n_reads < 0 || (n_reads > 0 && (!read_text || !read_off)) || !as || !xs || !seed ||
-        !strand || !pos || !nm || !cigar || cigar_stride < 1 || !n_cigar)
-        return tl_error.fail(SC_ERR_ARG, "sc_align_reads: missing argument");
-    if (n_seeds > MAX_SEEDS) return tl_error.fail(SC_ERR_UNSUPPORTED, "sc_align_reads: more than 1048575 seeds");
-    Packed sd, rd;
-    std::string why;
-    if (!sd.rebase(seed_off, n_seeds, MAX_COLS, "sc_align_reads", "seed", why) ||
-        (n_reads > 0 && !rd.rebase(read_off, n_reads, MAX_ROWS, "sc_align_reads", "read", why)))
-        return tl_error.fail(SC_ERR_UNSUPPORTED, why);
-    long max_len = 0;
-    for (int r = 0; r < n_reads; r++) max_len = std::max(max_len, rd.len(r));
-    if (cigar_stride < max_len / 2 + 4) return tl_error.fail(SC_ERR_CAPACITY, "sc_align_reads: cigar_stride below max read length / 2 + 4");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return tl_error.fail(SC_ERR_NO_DEVICE, "no HIP device");
-    if (hipSetDevice(device) != hipSuccess) return tl_error.fail(SC_ERR_HIP, "hipSetDevice failed");
-    if (n_reads == 0) return SC_OK;
-    const double t0 = sc::now_ms();
-    // ---- host packing: seed codes, read code | penalty << 4, reads bucketed by rows per lane
-    sd.pack(seed_text + seed_off[0], [](long, int c) { return c < 0 ? REF_OTHER : c; });
-    rd.pack(read_text + read_off[0], [&](long k, int c) {
-        int q = qual_text ? (int)(unsigned char)qual_text[read_off[0] + k] - 33 : 40;
-        q = std::min(std::max(q, 0), 40);
-        const int pen = c < 0 ? 1 : 2 + q / 10;
-        return (c < 0 ? 4 : c) | (pen << 4);
-    });
-    Buckets by_r;
-    for (int r = 0; r < n_reads; r++) by_r.add(r, rd.len(r));
-    const std::vector<int> rids = by_r.order();
-    // ---- device: the score pass
-    sc::DevMem<uint8_t> d_sq(sd.codes.size()), d_rq(rd.codes.size());
-    sc::DevMem<long> d_so(sd.off.size()), d_ro(rd.off.size());
-    sc::DevMem<int> d_rids(rids.size());
-    sc::DevMem<unsigned long long> d_best((size_t)n_reads), d_second((size_t)n_reads);
-    sc::TimedStream st;
-    st.mark("upload");
-    st.h2d(d_sq, sd.codes); st.h2d(d_so, sd.off); st.h2d(d_rq, rd.codes); st.h2d(d_ro, rd.off); st.h2d(d_rids, rids);
-    st.zero(d_best.p, (size_t)n_reads * 8);
-    st.zero(d_second.p, (size_t)n_reads * 8);
-    st.mark("score");
-    by_r.each([&](auto r, long at, const std::vector<int>& ids) {
-        const long n_tiles = (long)ids.size() * 2L * n_seeds;
-        hipLaunchKernelGGL(k_sw_score<decltype(r)::value>, score_grid(n_tiles), dim3(64 * SCORE_WAVES), 0, st, d_sq.p, d_so.p, n_seeds, d_rq.p,
-                           d_ro.p, d_rids.p + at, n_tiles, d_best.p, d_second.p);
-        st.launched();
-        if (stats) for (int id : ids) stats->score_cells += 2L * rd.len(id) * sd.bytes();
-    });
-    st.mark("scored");
-    std::vector<unsigned long long> best((size_t)n_reads), second((size_t)n_reads);
-    st.d2h(best, d_best); st.d2h(second, d_second);
-    st.sync();
-    // ---- which reads align; the traceback of those, bucketed by rows per lane again
-    Buckets tr_r;
-    for (int r = 0; r < n_reads; r++) {
-        const double thr = 20.0 + 8.0 * std::log((double)rd.len(r));
-        const int S = key_score(best[(size_t)r]), X = key_score(second[(size_t)r]);
-        as[r] = S;
-        xs[r] = (double)X >= thr ? X : -1;
-        seed[r] = -1; strand[r] = 0; pos[r] = 0; nm[r] = 0; n_cigar[r] = 0;
-        if ((double)S >= thr) tr_r.add(r, rd.len(r));
-    }
-    const std::vector<int> tids = tr_r.order();
-    const int n_tr = (int)tids.size();
-    std::vector<int> tout((size_t)n_tr * 4);
-    std::vector<unsigned> tcig((size_t)n_tr * (size_t)cigar_stride);
-    sc::DevMem<int> d_tids((size_t)n_tr), d_out(tout.size());
-    sc::DevMem<unsigned> d_cig(tcig.size());
-    st.h2d(d_tids, tids);
-    st.mark("trace");
-    tr_r.each([&](auto r, long at, const std::vector<int>& ids) {
-        hipLaunchKernelGGL(k_sw_trace<decltype(r)::value>, trace_grid((int)ids.size()), dim3(64), 0, st, d_sq.p, d_so.p, d_rq.p, d_ro.p,
-                           d_tids.p + at, (int)ids.size(), d_best.p, d_out.p + 4 * at, d_cig.p + at * cigar_stride, cigar_stride);
-        st.launched();
-    });
-    st.mark("traced");
-    st.d2h(tout, d_out); st.d2h(tcig, d_cig);
-    st.sync();
-    int rc = SC_OK;
-    for (int t = 0; t < n_tr; t++) {
-        const int r = tids[(size_t)t];
-        const unsigned long long key = best[(size_t)r];
-        if (tout[(size_t)t * 4] < 0) { rc = tl_error.fail(SC_ERR_INTERNAL, "sc_align_reads: traceback of read " + std::to_string(r) + " failed"); break; }
-        seed[r] = key_seed(key);
-        strand[r] = key_strand(key);
-        pos[r] = tout[(size_t)t * 4] + 1;
-        nm[r] = tout[(size_t)t * 4 + 2];
-        n_cigar[r] = tout[(size_t)t * 4 + 3];
-        std::memcpy(cigar + (long)r * cigar_stride, tcig.data() + (size_t)t * cigar_stride, sizeof(unsigned) * (size_t)n_cigar[r]);
-        if (stats) {
-            const int nrows = key_row(key) + 1;
-            stats->trace_cells += window_cells(trace_window<SwCell>(key_score(key), key_col(key), nrows), nrows, 0);
+    return sc::guarded(&tl_error, "sc_align_reads", [&] {
+        if (!seed_text || !seed_off || n_seeds < 1 || n_reads < 0 || (n_reads > 0 && (!read_text || !read_off)) || !as || !xs || !seed ||
+            !strand || !pos || !nm || !cigar || cigar_stride < 1 || !n_cigar)
+            return tl_error.fail(SC_ERR_ARG, "sc_align_reads: missing argument");
+        if (n_seeds > MAX_SEEDS) return tl_error.fail(SC_ERR_UNSUPPORTED, "sc_align_reads: more than 1048575 seeds");
+        Packed sd, rd;
+        std::string why;
+        if (!sd.rebase(seed_off, n_seeds, MAX_COLS, "sc_align_reads", "seed", why) ||
+            (n_reads > 0 && !rd.rebase(read_off, n_reads, MAX_ROWS, "sc_align_reads", "read", why)))
+            return tl_error.fail(SC_ERR_UNSUPPORTED, why);
+        long max_len = 0;
+        for (int r = 0; r < n_reads; r++) max_len = std::max(max_len, rd.len(r));
+        if (cigar_stride < max_len / 2 + 4) return tl_error.fail(SC_ERR_CAPACITY, "sc_align_reads: cigar_stride below max read length / 2 + 4");
+        sc::select_device(device);
+        if (n_reads == 0) return SC_OK;
+        const double t0 = sc::now_ms();
+        // ---- host packing: seed codes, read code | penalty << 4, reads bucketed by rows per lane
+        sd.pack(seed_text + seed_off[0], [](long, int c) { return c < 0 ? REF_OTHER : c; });
+        rd.pack(read_text + read_off[0], [&](long k, int c) {
+            int q = qual_text ? (int)(unsigned char)qual_text[read_off[0] + k] - 33 : 40;
+            q = std::min(std::max(q, 0), 40);
+            const int pen = c < 0 ? 1 : 2 + q / 10;
+            return (c < 0 ? 4 : c) | (pen << 4);
+        });
+        Buckets by_r;
+        for (int r = 0; r < n_reads; r++) by_r.add(r, rd.len(r));
+        const std::vector<int> rids = by_r.order();
+        // ---- device: the score pass
+        sc::DevMem<uint8_t> d_sq(sd.codes.size()), d_rq(rd.codes.size());
+        sc::DevMem<long> d_so(sd.off.size()), d_ro(rd.off.size());
+        sc::DevMem<int> d_rids(rids.size());
+        sc::DevMem<unsigned long long> d_best((size_t)n_reads), d_second((size_t)n_reads);
+        sc::TimedStream st;
+        st.mark("upload");
+        st.h2d(d_sq, sd.codes); st.h2d(d_so, sd.off); st.h2d(d_rq, rd.codes); st.h2d(d_ro, rd.off); st.h2d(d_rids, rids);
+        st.zero(d_best.p, (size_t)n_reads * 8);
+        st.zero(d_second.p, (size_t)n_reads * 8);
+        st.mark("score");
+        by_r.each([&](auto r, long at, const std::vector<int>& ids) {
+            const long n_tiles = (long)ids.size() * 2L * n_seeds;
+            hipLaunchKernelGGL(k_sw_score<decltype(r)::value>, score_grid(n_tiles), dim3(64 * SCORE_WAVES), 0, st, d_sq.p, d_so.p, n_seeds, d_rq.p,
+                               d_ro.p, d_rids.p + at, n_tiles, d_best.p, d_second.p);
+            st.launched();
+            if (stats) for (int id : ids) stats->score_cells += 2L * rd.len(id) * sd.bytes();
+        });
+        st.mark("scored");
+        std::vector<unsigned long long> best((size_t)n_reads), second((size_t)n_reads);
+        st.d2h(best, d_best); st.d2h(second, d_second);
+        st.sync();
+        // ---- which reads align; the traceback of those, bucketed by rows per lane again
+        Buckets tr_r;
+        for (int r = 0; r < n_reads; r++) {
+            const double thr = 20.0 + 8.0 * std::log((double)rd.len(r));
+            const int S = key_score(best[(size_t)r]), X = key_score(second[(size_t)r]);
+            as[r] = S;
+            xs[r] = (double)X >= thr ? X : -1;
+            seed[r] = -1; strand[r] = 0; pos[r] = 0; nm[r] = 0; n_cigar[r] = 0;
+            if ((double)S >= thr) tr_r.add(r, rd.len(r));
         }
-    }
-    if (stats && rc == SC_OK) {
-        read_phase_ms(st, stats);
-        stats->n_traced = n_tr;
-    }
-    if (stats) stats->total_ms = sc::now_ms() - t0;
-    return rc;
-} catch (const sc::HipError&) {
-    return tl_error.fail(SC_ERR_HIP, "sc_align_reads: a HIP call failed");
+        const std::vector<int> tids = tr_r.order();
+        const int n_tr = (int)tids.size();
+        std::vector<int> tout((size_t)n_tr * 4);
+        std::vector<unsigned> tcig((size_t)n_tr * (size_t)cigar_stride);
+        sc::DevMem<int> d_tids((size_t)n_tr), d_out(tout.size());
+        sc::DevMem<unsigned> d_cig(tcig.size());
+        st.h2d(d_tids, tids);
+        st.mark("trace");
+        tr_r.each([&](auto r, long at, const std::vector<int>& ids) {
+            hipLaunchKernelGGL(k_sw_trace<decltype(r)::value>, trace_grid((int)ids.size()), dim3(64), 0, st, d_sq.p, d_so.p, d_rq.p, d_ro.p,
+                               d_tids.p + at, (int)ids.size(), d_best.p, d_out.p + 4 * at, d_cig.p + at * cigar_stride, cigar_stride);
+            st.launched();
+        });
+        st.mark("traced");
+        st.d2h(tout, d_out); st.d2h(tcig, d_cig);
+        st.sync();
+        int rc = SC_OK;
+        for (int t = 0; t < n_tr; t++) {
+            const int r = tids[(size_t)t];
+            const unsigned long long key = best[(size_t)r];
+            if (tout[(size_t)t * 4] < 0) { rc = tl_error.fail(SC_ERR_INTERNAL, "sc_align_reads: traceback of read " + std::to_string(r) + " failed"); break; }
+            seed[r] = key_seed(key);
+            strand[r] = key_strand(key);
+            pos[r] = tout[(size_t)t * 4] + 1;
+            nm[r] = tout[(size_t)t * 4 + 2];
+            n_cigar[r] = tout[(size_t)t * 4 + 3];
+            std::memcpy(cigar + (long)r * cigar_stride, tcig.data() + (size_t)t * cigar_stride, sizeof(unsigned) * (size_t)n_cigar[r]);
+            if (stats) {
+                const int nrows = key_row(key) + 1;
+                stats->trace_cells += window_cells(trace_window<SwCell>(key_score(key), key_col(key), nrows), nrows, 0);
+            }
+        }
+        if (stats && rc == SC_OK) {
+            read_phase_ms(st, stats);
+            stats->n_traced = n_tr;
+        }
+        if (stats) stats->total_ms = sc::now_ms() - t0;
+        return rc;
+    });
 }
 
 }  // extern "C"

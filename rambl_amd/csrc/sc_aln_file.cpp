@@ -258,35 +258,37 @@ int sc_aln_open(const char* path, sc_aln** out) { return sc_aln_open_filtered(pa
 int sc_aln_open_filtered(const char* path, const char* const* names, int n_names, sc_aln** out) {
     if (!path || !out || (n_names > 0 && !names)) return SC_ERR_ARG;
     *out = nullptr;
-    std::unique_ptr<sc_aln> a(new sc_aln());
-    if (n_names >= 0) {
-        a->keep_all = false;
-        for (int i = 0; i < n_names; i++) if (names[i]) a->keep.insert(names[i]);
-    }
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return SC_ERR_ARG;
-    struct stat stt;
-    if (fstat(fd, &stt) != 0) { close(fd); return SC_ERR_ARG; }
-    a->map_len = (size_t)stt.st_size;
-    bool ok = true;
-    if (a->map_len > 0) {
-        a->map = mmap(nullptr, a->map_len, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (a->map == MAP_FAILED) { a->map = nullptr; close(fd); return SC_ERR_INTERNAL; }
-        const unsigned char* b = (const unsigned char*)a->map;
-        try {
-            if (a->map_len >= 2 && b[0] == 0x1f && b[1] == 0x8b) {
-                ok = load_bam(*a, b, a->map_len);
-                munmap(a->map, a->map_len);            // every string was copied out
-                a->map = nullptr;
-            } else {
-                ok = load_sam_text(*a, (const char*)a->map, a->map_len);
-            }
-        } catch (const std::bad_alloc&) { a->error = "out of memory while reading the alignments"; ok = false; }
-        catch (const std::exception& ex) { a->error = ex.what(); ok = false; }
-    }
-    close(fd);
-    *out = a.release();
-    return ok ? SC_OK : SC_ERR_ARG;                // on a parse error the handle carries the message (sc_aln_error)
+    return sc::guarded(nullptr, "sc_aln_open", [&] {          // the handle's own message needs a handle: without one, the code alone
+        std::unique_ptr<sc_aln> a(new sc_aln());
+        if (n_names >= 0) {
+            a->keep_all = false;
+            for (int i = 0; i < n_names; i++) if (names[i]) a->keep.insert(names[i]);
+        }
+        const int fd = open(path, O_RDONLY);
+        if (fd < 0) return SC_ERR_ARG;
+        struct stat stt;
+        if (fstat(fd, &stt) != 0) { close(fd); return SC_ERR_ARG; }
+        a->map_len = (size_t)stt.st_size;
+        bool ok = true;
+        if (a->map_len > 0) {
+            a->map = mmap(nullptr, a->map_len, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (a->map == MAP_FAILED) { a->map = nullptr; close(fd); return SC_ERR_INTERNAL; }
+            const unsigned char* b = (const unsigned char*)a->map;
+            try {
+                if (a->map_len >= 2 && b[0] == 0x1f && b[1] == 0x8b) {
+                    ok = load_bam(*a, b, a->map_len);
+                    munmap(a->map, a->map_len);            // every string was copied out
+                    a->map = nullptr;
+                } else {
+                    ok = load_sam_text(*a, (const char*)a->map, a->map_len);
+                }
+            } catch (const std::bad_alloc&) { a->error = "out of memory while reading the alignments"; ok = false; }
+            catch (const std::exception& ex) { a->error = ex.what(); ok = false; }
+        }
+        close(fd);
+        *out = a.release();
+        return ok ? SC_OK : SC_ERR_ARG;                // on a parse error the handle carries the message (sc_aln_error)
+    });
 }
 
 void sc_aln_close(sc_aln* a) { delete a; }
@@ -295,38 +297,42 @@ long sc_aln_records(sc_aln* a) { return a ? a->n_records : 0; }
 
 int sc_aln_ref_stats(sc_aln* a, const char* gene, long* n_records, long* aligned_bases) {
     if (!a || !gene) return SC_ERR_ARG;
-    long n = 0, b = 0;
-    auto it = a->stats.find(gene);
-    if (it != a->stats.end()) { n = it->second.n; b = it->second.bases; }
-    if (n_records) *n_records = n;
-    if (aligned_bases) *aligned_bases = b;
-    return SC_OK;
+    return sc::guarded(nullptr, "sc_aln_ref_stats", [&] {      // the key of the look-up is a string
+        long n = 0, b = 0;
+        auto it = a->stats.find(gene);
+        if (it != a->stats.end()) { n = it->second.n; b = it->second.bases; }
+        if (n_records) *n_records = n;
+        if (aligned_bases) *aligned_bases = b;
+        return SC_OK;
+    });
 }
 
 int sc_aln_walk(sc_aln* a, long first, long n, char* buf, long cap, long* n_out, long* len_out) {
     if (!a || first < 0 || n < 0 || (n > 0 && !buf) || !n_out || !len_out) return SC_ERR_ARG;
-    std::call_once(a->order_once, [a] {
-        a->order.reserve((size_t)a->n_records);
-        for (auto& kv : a->by_ref) for (const Rec& r : kv.second) a->order.push_back(&r);
-        std::sort(a->order.begin(), a->order.end(), [](const Rec* x, const Rec* y) { return x->ord < y->ord; });
+    return sc::guarded(nullptr, "sc_aln_walk", [&] {
+        std::call_once(a->order_once, [a] {
+            a->order.reserve((size_t)a->n_records);
+            for (auto& kv : a->by_ref) for (const Rec& r : kv.second) a->order.push_back(&r);
+            std::sort(a->order.begin(), a->order.end(), [](const Rec* x, const Rec* y) { return x->ord < y->ord; });
+        });
+        *n_out = 0; *len_out = 0;
+        long used = 0, k = 0;
+        for (; k < n && first + k < (long)a->order.size(); k++) {
+            const Rec& r = *a->order[(size_t)(first + k)];
+            char num[16];
+            const int nl = snprintf(num, sizeof num, "%d", r.flag);
+            const long need = (long)r.qlen + nl + r.slen + r.quallen + 4;
+            if (used + need > cap) break;
+            char* o = buf + used;
+            memcpy(o, r.qname, (size_t)r.qlen); o += r.qlen; *o++ = '\t';
+            memcpy(o, num, (size_t)nl); o += nl; *o++ = '\t';
+            memcpy(o, r.seq, (size_t)r.slen); o += r.slen; *o++ = '\t';
+            memcpy(o, r.qual, (size_t)r.quallen); o += r.quallen; *o++ = '\n';
+            used += need;
+        }
+        *n_out = k; *len_out = used;
+        return (k == 0 && n > 0 && first < (long)a->order.size()) ? SC_ERR_CAPACITY : SC_OK;
     });
-    *n_out = 0; *len_out = 0;
-    long used = 0, k = 0;
-    for (; k < n && first + k < (long)a->order.size(); k++) {
-        const Rec& r = *a->order[(size_t)(first + k)];
-        char num[16];
-        const int nl = snprintf(num, sizeof num, "%d", r.flag);
-        const long need = (long)r.qlen + nl + r.slen + r.quallen + 4;
-        if (used + need > cap) break;
-        char* o = buf + used;
-        memcpy(o, r.qname, (size_t)r.qlen); o += r.qlen; *o++ = '\t';
-        memcpy(o, num, (size_t)nl); o += nl; *o++ = '\t';
-        memcpy(o, r.seq, (size_t)r.slen); o += r.slen; *o++ = '\t';
-        memcpy(o, r.qual, (size_t)r.quallen); o += r.quallen; *o++ = '\n';
-        used += need;
-    }
-    *n_out = k; *len_out = used;
-    return (k == 0 && n > 0 && first < (long)a->order.size()) ? SC_ERR_CAPACITY : SC_OK;
 }
 
 }  // extern "C"

@@ -54,6 +54,14 @@ struct LevelStub {
 
 struct sc_ctx { Ctx c; sc_ctx(int device, const CtxPlan& plan) : c(device, plan) {} };
 
+// sc::guarded for an entry on a context: the message goes to sc_last_error(), under the context's mutex.
+template <class F> static int ctx_guarded(Ctx* ctx, const char* fn, F&& body) noexcept {
+    LastError err;
+    const int rc = guarded(&err, fn, body);
+    if (!err.text.empty()) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error.swap(err.text); }
+    return rc;
+}
+
 extern "C" {
 
 // Host threads a context with `stream_count` regions in flight starts on a rank that shares its host with
@@ -72,50 +80,45 @@ int sc_ctx_create(int device, int stream_count, sc_ctx** out) {
     // 16 hardware queues run side by side on this GPU (more are time-sliced: measured); the launch and setup streams of the
     // context want one each.  Only effective if HIP is not initialised yet in this process (rambl_amd/__init__.py sets it too).
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return SC_ERR_NO_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return SC_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SC_ERR_NO_DEVICE;   // kernels are built for gfx950 only
-    if (hipSetDevice(device) != hipSuccess) return SC_ERR_HIP;
-    if (init_kernels() != 0) return SC_ERR_HIP;
-    const Options opt = read_options();
-    // the context's threads (they inherit the mask of the thread that starts them) and the host memory it allocates and first
-    // touches here: next to the GPU; the caller's own mask comes back when this function returns
-    struct Near {
-        cpu_set_t before; bool moved = false;
-        Near(int dev, bool bind) {
-            cpu_set_t local;
-            if (bind && sched_getaffinity(0, sizeof before, &before) == 0 && sc::gpu_local_cpus(dev, &local)) moved = sched_setaffinity(0, sizeof local, &local) == 0;
+    return guarded(nullptr, "sc_ctx_create", [&] {            // no context yet to keep a message: the code alone
+        select_device(device);
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) != hipSuccess) return SC_ERR_NO_DEVICE;
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SC_ERR_NO_DEVICE;   // kernels are built for gfx950 only
+        if (init_kernels() != 0) return SC_ERR_HIP;
+        const Options opt = read_options();
+        // the context's threads (they inherit the mask of the thread that starts them) and the host memory it allocates and first
+        // touches here: next to the GPU; the caller's own mask comes back when this function returns
+        struct Near {
+            cpu_set_t before; bool moved = false;
+            Near(int dev, bool bind) {
+                cpu_set_t local;
+                if (bind && sched_getaffinity(0, sizeof before, &before) == 0 && sc::gpu_local_cpus(dev, &local)) moved = sched_setaffinity(0, sizeof local, &local) == 0;
+            }
+            ~Near() { if (moved) (void)sched_setaffinity(0, sizeof before, &before); }
+        } near{device, !opt.off(opt.numa_bind)};
+        {
+            // A region builds its graph out of ~10^5 small allocations and a few of tens of megabytes; handed back to the system
+            // and mapped again for every region they cost their size in page faults.  Keep freed memory in the process.
+            static std::once_flag once;
+            std::call_once(once, [&opt] {
+                if (opt.off(opt.malloc_tune)) return;
+                mallopt(M_MMAP_THRESHOLD, 32 << 20);
+                mallopt(M_TRIM_THRESHOLD, 1 << 30);
+                mallopt(M_TOP_PAD, 64 << 20);
+            });
         }
-        ~Near() { if (moved) (void)sched_setaffinity(0, sizeof before, &before); }
-    } near{device, !opt.off(opt.numa_bind)};
-    {
-        // A region builds its graph out of ~10^5 small allocations and a few of tens of megabytes; handed back to the system
-        // and mapped again for every region they cost their size in page faults.  Keep freed memory in the process.
-        static std::once_flag once;
-        std::call_once(once, [&opt] {
-            if (opt.off(opt.malloc_tune)) return;
-            mallopt(M_MMAP_THRESHOLD, 32 << 20);
-            mallopt(M_TRIM_THRESHOLD, 1 << 30);
-            mallopt(M_TOP_PAD, 64 << 20);
-        });
-    }
-    try {
         *out = new sc_ctx(device, plan_context(opt, stream_count, prop.multiProcessorCount, cpu_budget_host(), local_world_size()));
-    } catch (const std::exception&) {
-        return SC_ERR_HIP;
-    }
-    return SC_OK;
+        return SC_OK;
+    });
 }
 
 void sc_ctx_destroy(sc_ctx* h) { delete h; }
 
 const char* sc_last_error(sc_ctx* h) {
     if (!h) return "";
-    std::lock_guard<std::mutex> lk(h->c.mu);
     static thread_local std::string copy;
-    copy = h->c.last_error;
+    if (guarded(nullptr, "sc_last_error", [&] { std::lock_guard<std::mutex> lk(h->c.mu); copy = h->c.last_error; return SC_OK; }) != SC_OK) return "";
     return copy.c_str();
 }
 
@@ -139,37 +142,39 @@ int sc_roi_submit(sc_ctx* h, const char* ref_bases, int ref_len, const int* read
     for (int i = 0; i < n_reads; i++)
         if (read_copies[i] < 1 || cigar_off[i + 1] < cigar_off[i] || seq_off[i + 1] < seq_off[i] || mate_off[i + 1] < mate_off[i])
             return SC_ERR_ARG;
-    auto job = std::make_shared<Job>();
-    job->t_submit = now_ms();
-    job->ref.assign(ref_bases, (size_t)ref_len);
-    job->reads.resize((size_t)n_reads);
-    for (int i = 0; i < n_reads; i++) {
-        if (read_pos[i] < 0 || read_pos[i] > ref_len) return SC_ERR_ARG;
-        job->reads[i].pos = read_pos[i];
-        job->reads[i].cigar.assign(cigar_text + cigar_off[i], (size_t)(cigar_off[i + 1] - cigar_off[i]));
-        job->reads[i].seq.assign(seq_text + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
-        job->reads[i].cn = read_copies[i];
-    }
-    job->mate_off.assign(mate_off ? mate_off : nullptr, mate_off ? mate_off + n_reads + 1 : nullptr);
-    if (job->mate_off.empty()) job->mate_off.assign(1, 0);
-    const int nm = job->mate_off.back();
-    if (nm > 0 && !mate_idx) return SC_ERR_ARG;
-    job->mate_idx.assign(mate_idx, mate_idx + nm);
-    for (int v : job->mate_idx) if (v < -1 || v >= n_reads) return SC_ERR_ARG;
-    job->params = *params;
     Ctx* ctx = &h->c;
-    Worker* wake = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        job->handle = ctx->next_handle++;
-        ctx->jobs[job->handle] = job;
-        ctx->queue.push_back(job);
-        ctx->regions_active.fetch_add(1, std::memory_order_acq_rel);
-        *handle_out = job->handle;
-        if (!ctx->idle.empty()) { wake = ctx->idle.back(); ctx->idle.pop_back(); }
-    }
-    if (wake) ctx->pool->make_ready(wake->fib);
-    return SC_OK;
+    return ctx_guarded(ctx, "sc_roi_submit", [&] {
+        auto job = std::make_shared<Job>();
+        job->t_submit = now_ms();
+        job->ref.assign(ref_bases, (size_t)ref_len);
+        job->reads.resize((size_t)n_reads);
+        for (int i = 0; i < n_reads; i++) {
+            if (read_pos[i] < 0 || read_pos[i] > ref_len) return SC_ERR_ARG;
+            job->reads[i].pos = read_pos[i];
+            job->reads[i].cigar.assign(cigar_text + cigar_off[i], (size_t)(cigar_off[i + 1] - cigar_off[i]));
+            job->reads[i].seq.assign(seq_text + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+            job->reads[i].cn = read_copies[i];
+        }
+        job->mate_off.assign(mate_off ? mate_off : nullptr, mate_off ? mate_off + n_reads + 1 : nullptr);
+        if (job->mate_off.empty()) job->mate_off.assign(1, 0);
+        const int nm = job->mate_off.back();
+        if (nm > 0 && !mate_idx) return SC_ERR_ARG;
+        job->mate_idx.assign(mate_idx, mate_idx + nm);
+        for (int v : job->mate_idx) if (v < -1 || v >= n_reads) return SC_ERR_ARG;
+        job->params = *params;
+        Worker* wake = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            job->handle = ctx->next_handle++;
+            ctx->jobs[job->handle] = job;
+            ctx->queue.push_back(job);
+            ctx->regions_active.fetch_add(1, std::memory_order_acq_rel);
+            *handle_out = job->handle;
+            if (!ctx->idle.empty()) { wake = ctx->idle.back(); ctx->idle.pop_back(); }
+        }
+        if (wake) ctx->pool->make_ready(wake->fib);
+        return SC_OK;
+    });
 }
 
 static std::shared_ptr<Job> find_job(sc_ctx* h, int handle) {
@@ -182,10 +187,12 @@ int sc_roi_wait(sc_ctx* h, int handle) {
     if (!h) return SC_ERR_ARG;
     auto job = find_job(h, handle);
     if (!job) return SC_ERR_ARG;
-    std::unique_lock<std::mutex> lk(h->c.mu);
-    h->c.cv_done.wait(lk, [&] { return job->status == 1; });
-    if (job->rc != SC_OK) h->c.last_error = job->err;
-    return job->rc;
+    return ctx_guarded(&h->c, "sc_roi_wait", [&] {            // the copy of the message allocates
+        std::unique_lock<std::mutex> lk(h->c.mu);
+        h->c.cv_done.wait(lk, [&] { return job->status == 1; });
+        if (job->rc != SC_OK) h->c.last_error = job->err;
+        return job->rc;
+    });
 }
 
 int sc_roi_result(sc_ctx* h, int handle, char* seq_buf, long seq_cap, int* seq_off, double* abundance, int max_strains,
@@ -289,7 +296,7 @@ int sc_edge_support_tables(sc_ctx* h, int n_nodes, const int* pool_ptr, const in
             for (int x = pool_ptr[a] + 1; x < pool_ptr[a + 1]; x++) if (pool_rid[x] < pool_rid[x - 1]) return SC_ERR_ARG;
     if (n_edges == 0) return SC_OK;
     Ctx* ctx = &h->c;
-    try {
+    return ctx_guarded(ctx, "sc_edge_support_tables", [&] {
         Worker w;                                      // a private worker: own stream
         w.init_private(ctx);
         const hipStream_t st = w.st;
@@ -309,8 +316,7 @@ int sc_edge_support_tables(sc_ctx* h, int n_nodes, const int* pool_ptr, const in
         HIPCHK(hipMemcpyAsync(support_out, d_sup, sizeof(int) * (size_t)n_edges, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return SC_OK;
-    } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
-    catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
+    });
 }
 int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const double* ll, const unsigned char* has, int n_ent,
                     int e0, const int* ent_rid, const int* ent_cn, const int* ent_sym, const int* mate_off, const int* mate_idx,
@@ -335,7 +341,7 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
     const int nm = mate_off[n_reads];
     if (nm > 0 && !mate_idx) return SC_ERR_ARG;
     for (int i = 0; i < nm; i++) if (mate_idx[i] < -1 || mate_idx[i] >= n_reads) return SC_ERR_ARG;
-    try {
+    return ctx_guarded(ctx, "sc_sample_level", [&] {
         Worker w;                                      // a private worker: own stream, own parameter / result blocks
         w.init_private(ctx);
         const int E = e0 + n_ent;
@@ -386,8 +392,7 @@ int sc_sample_level(sc_ctx* h, int S, const double* a0, int n_reads, const doubl
         std::memcpy(cnt, R.cnt, sizeof(unsigned) * (size_t)S * KMAX);
         out[0] = (long)R.n_draws; out[1] = (long)R.n_slow; out[2] = (long)R.n_exact; out[3] = (long)R.n_pass; out[4] = kind; out[5] = done;
         return SC_OK;
-    } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
-    catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
+    });
 }
 int sc_update_level(sc_ctx* h, int S, const int* slot, const int* lab_off, const int* lab_len, int K, int code_N, const double* lpt,
                     int n_reads, const double* ll, const unsigned char* has, const unsigned char* labels, int n_labels, int n_ent,
@@ -439,7 +444,7 @@ int sc_update_level(sc_ctx* h, int S, const int* slot, const int* lab_off, const
         set(dst_rows, copy_dst[c]); set(src_rows, copy_src[c]);
     }
     if ((dst_rows[0] & src_rows[0]) || (dst_rows[1] & src_rows[1])) return SC_ERR_ARG;
-    try {
+    return ctx_guarded(ctx, "sc_update_level", [&] {
         Worker w;                                      // a private worker: own stream, own parameter / result blocks
         w.init_private(ctx);
         const int E = e0 + n_ent;
@@ -488,8 +493,7 @@ int sc_update_level(sc_ctx* h, int S, const int* slot, const int* lab_off, const
         HIPCHK(hipMemcpy(isnew_out, jd.isnew, (size_t)n_ent, hipMemcpyDeviceToHost));
         *done_out = done;
         return SC_OK;
-    } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
-    catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
+    });
 }
 int sc_roi_release(sc_ctx* h, int handle) {
     if (!h) return SC_ERR_ARG;
@@ -504,7 +508,7 @@ int sc_msa_align(sc_ctx* h, const char* seq_text, const int* seq_off, int n, cha
     if (!h || !seq_text || !seq_off || n < 1 || !ncol_out) return SC_ERR_ARG;
     Ctx* ctx = &h->c;
     // runs on a private worker object (own stream) so it can be called while regions are in flight
-    try {
+    return ctx_guarded(ctx, "sc_msa_align", [&] {
         Worker w;
         w.init_private(ctx);
         std::vector<std::string> seqs((size_t)n), rows;
@@ -517,8 +521,7 @@ int sc_msa_align(sc_ctx* h, const char* seq_text, const int* seq_off, int n, cha
         if (!rows_out || (long)n * (ncol + 1) > cap) rc = SC_ERR_CAPACITY;
         else for (int i = 0; i < n; i++) { std::memcpy(rows_out + (long)i * (ncol + 1), rows[i].data(), (size_t)ncol); rows_out[(long)i * (ncol + 1) + ncol] = 0; }
         return rc;
-    } catch (const ScError& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return ex.code; }
-    catch (const std::exception& ex) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error = ex.what(); return SC_ERR_HIP; }
+    });
 }
 
 }  // extern "C"

@@ -291,91 +291,88 @@ extern "C" {
 
 int sc_depth_scan_runs(int device, const int* ref_len, int n_refs, const int* run_ref, const int* run_start, const int* run_end,
                        long n_runs, int max_gap, int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap,
-                       int* n_intervals, sc_depth_stats* stats) try {
-    if (!ref_len || n_refs < 0 || n_runs < 0 || (n_runs > 0 && (!run_ref || !run_start || !run_end)) || !n_intervals) return SC_ERR_ARG;
-    if (!depth_limits_ok(ref_len, n_refs, max_gap)) return SC_ERR_ARG;
-    if (n_runs > 0xFFFFFFF0L) return SC_ERR_CAPACITY;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SC_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return SC_ERR_HIP;
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    const double t0 = sc::now_ms();
-    // bucket the runs by reference (a counting sort: the order inside a reference is kept)
-    std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
-    for (long i = 0; i < n_runs; i++) {
-        const int r = run_ref[i];
-        if (r < 0 || r >= n_refs || run_start[i] < 1 || run_end[i] < run_start[i] || run_end[i] > ref_len[r]) return SC_ERR_ARG;      // 1-based, inclusive
-        ptr[(size_t)r + 1]++;
-    }
-    for (int r = 0; r < n_refs; r++) ptr[(size_t)r + 1] += ptr[(size_t)r];
-    sc::PinMem<uint2> pin((size_t)n_runs);
-    uint2* runs = pin.p;
-    std::vector<unsigned> cur(ptr.begin(), ptr.end() - 1);
-    int max_run = 1;
-    for (long i = 0; i < n_runs; i++) {
-        runs[cur[(size_t)run_ref[i]]++] = make_uint2((unsigned)(run_start[i] - 1), (unsigned)(run_end[i] - 1));
-        max_run = std::max(max_run, run_end[i] - run_start[i] + 1);
-    }
-    sort_long_refs(ref_len, n_refs, ptr.data(), runs);
-    if (stats) stats->prepare_ms = sc::now_ms() - t0;
-    return depth_scan_bucketed(ref_len, n_refs, ptr.data(), runs, n_runs, max_run, max_gap, iv_ref, iv_start, iv_end, iv_sum, iv_n, cap,
-                               n_intervals, stats);
-} catch (const sc::HipError&) {
-    return SC_ERR_HIP;
+                       int* n_intervals, sc_depth_stats* stats) {
+    // (no sc_depth_error(): the codes alone)
+    return sc::guarded(nullptr, "sc_depth_scan_runs", [&] {
+        if (!ref_len || n_refs < 0 || n_runs < 0 || (n_runs > 0 && (!run_ref || !run_start || !run_end)) || !n_intervals) return SC_ERR_ARG;
+        if (!depth_limits_ok(ref_len, n_refs, max_gap)) return SC_ERR_ARG;
+        if (n_runs > 0xFFFFFFF0L) return SC_ERR_CAPACITY;
+        sc::select_device(device);
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        const double t0 = sc::now_ms();
+        // bucket the runs by reference (a counting sort: the order inside a reference is kept)
+        std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
+        for (long i = 0; i < n_runs; i++) {
+            const int r = run_ref[i];
+            if (r < 0 || r >= n_refs || run_start[i] < 1 || run_end[i] < run_start[i] || run_end[i] > ref_len[r]) return SC_ERR_ARG;      // 1-based, inclusive
+            ptr[(size_t)r + 1]++;
+        }
+        for (int r = 0; r < n_refs; r++) ptr[(size_t)r + 1] += ptr[(size_t)r];
+        sc::PinMem<uint2> pin((size_t)n_runs);
+        uint2* runs = pin.p;
+        std::vector<unsigned> cur(ptr.begin(), ptr.end() - 1);
+        int max_run = 1;
+        for (long i = 0; i < n_runs; i++) {
+            runs[cur[(size_t)run_ref[i]]++] = make_uint2((unsigned)(run_start[i] - 1), (unsigned)(run_end[i] - 1));
+            max_run = std::max(max_run, run_end[i] - run_start[i] + 1);
+        }
+        sort_long_refs(ref_len, n_refs, ptr.data(), runs);
+        if (stats) stats->prepare_ms = sc::now_ms() - t0;
+        return depth_scan_bucketed(ref_len, n_refs, ptr.data(), runs, n_runs, max_run, max_gap, iv_ref, iv_start, iv_end, iv_sum, iv_n, cap,
+                                   n_intervals, stats);
+    });
 }
 
 int sc_depth_scan(int device, sc_aln* const* alns, int n_alns, const char* const* ref_names, const int* ref_len, int n_refs, int max_gap,
-                  int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap, int* n_intervals, sc_depth_stats* stats) try {
-    if (!alns || n_alns < 0 || !ref_names || !ref_len || n_refs < 0 || !n_intervals) return SC_ERR_ARG;
-    if (!depth_limits_ok(ref_len, n_refs, max_gap)) return SC_ERR_ARG;
-    for (int f = 0; f < n_alns; f++) if (!alns[f]) return SC_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SC_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return SC_ERR_HIP;
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    // ---- the aligned runs of every reference, over all files: references are independent, so the host threads of this
-    // rank take them in turns (the CIGAR walk of 10^7 records is the longest part of the stage once the device needs 0.1 ms)
-    const double t0 = sc::now_ms();
-    std::vector<std::vector<uint2>> per_ref((size_t)n_refs);
-    std::atomic<int> max_run_all{1};
-    sc::parallel_items(n_refs, std::max(1, std::min(sc::ingest_threads(), n_refs / 64 + 1)), [&](int r) {
-        int max_run = 1;
-        std::vector<uint2>& out = per_ref[(size_t)r];
-        for (int f = 0; f < n_alns; f++) {
-            auto it = alns[f]->by_ref.find(ref_names[r]);
-            if (it == alns[f]->by_ref.end()) continue;
-            for (const sc_ingest::Rec& rec : it->second) {
-                if (rec.flag & 0x704) continue;                      // samtools depth: unmapped, secondary, QC fail, duplicate
-                int p = rec.pos;
-                sc_ingest::for_each_op(rec.cigar, rec.clen, [&](char op, long len) {
-                    if (op == 'M' || op == '=' || op == 'X') {
-                        const int a = std::max(p, 1), b = std::min(p + (int)len - 1, ref_len[r]);
-                        if (a <= b) { out.push_back(make_uint2((unsigned)(a - 1), (unsigned)(b - 1))); max_run = std::max(max_run, b - a + 1); }
-                        p += (int)len;
-                    } else if (op == 'D' || op == 'N') {
-                        p += (int)len;                                // a deleted / skipped base is no depth
-                    }
-                });
+                  int* iv_ref, int* iv_start, int* iv_end, long* iv_sum, int* iv_n, int cap, int* n_intervals, sc_depth_stats* stats) {
+    return sc::guarded(nullptr, "sc_depth_scan", [&] {
+        if (!alns || n_alns < 0 || !ref_names || !ref_len || n_refs < 0 || !n_intervals) return SC_ERR_ARG;
+        if (!depth_limits_ok(ref_len, n_refs, max_gap)) return SC_ERR_ARG;
+        for (int f = 0; f < n_alns; f++) if (!alns[f]) return SC_ERR_ARG;
+        sc::select_device(device);
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        // ---- the aligned runs of every reference, over all files: references are independent, so the host threads of this
+        // rank take them in turns (the CIGAR walk of 10^7 records is the longest part of the stage once the device needs 0.1 ms)
+        const double t0 = sc::now_ms();
+        std::vector<std::vector<uint2>> per_ref((size_t)n_refs);
+        std::atomic<int> max_run_all{1};
+        sc::parallel_items(n_refs, std::max(1, std::min(sc::ingest_threads(), n_refs / 64 + 1)), [&](int r) {
+            int max_run = 1;
+            std::vector<uint2>& out = per_ref[(size_t)r];
+            for (int f = 0; f < n_alns; f++) {
+                auto it = alns[f]->by_ref.find(ref_names[r]);
+                if (it == alns[f]->by_ref.end()) continue;
+                for (const sc_ingest::Rec& rec : it->second) {
+                    if (rec.flag & 0x704) continue;                      // samtools depth: unmapped, secondary, QC fail, duplicate
+                    int p = rec.pos;
+                    sc_ingest::for_each_op(rec.cigar, rec.clen, [&](char op, long len) {
+                        if (op == 'M' || op == '=' || op == 'X') {
+                            const int a = std::max(p, 1), b = std::min(p + (int)len - 1, ref_len[r]);
+                            if (a <= b) { out.push_back(make_uint2((unsigned)(a - 1), (unsigned)(b - 1))); max_run = std::max(max_run, b - a + 1); }
+                            p += (int)len;
+                        } else if (op == 'D' || op == 'N') {
+                            p += (int)len;                                // a deleted / skipped base is no depth
+                        }
+                    });
+                }
             }
-        }
-        int m = max_run_all.load();
-        while (max_run > m && !max_run_all.compare_exchange_weak(m, max_run)) {}
+            int m = max_run_all.load();
+            while (max_run > m && !max_run_all.compare_exchange_weak(m, max_run)) {}
+        });
+        if (stats) stats->extract_ms = sc::now_ms() - t0;
+        const double t1 = sc::now_ms();
+        std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
+        unsigned long long total = 0;
+        for (int r = 0; r < n_refs; r++) { total += per_ref[(size_t)r].size(); if (total > 0xFFFFFFF0ull) return SC_ERR_CAPACITY; ptr[(size_t)r + 1] = (unsigned)total; }
+        sc::PinMem<uint2> pin((size_t)total);
+        uint2* runs = pin.p;
+        for (int r = 0; r < n_refs; r++)
+            if (!per_ref[(size_t)r].empty()) std::memcpy(runs + ptr[(size_t)r], per_ref[(size_t)r].data(), sizeof(uint2) * per_ref[(size_t)r].size());
+        sort_long_refs(ref_len, n_refs, ptr.data(), runs);
+        if (stats) stats->prepare_ms = sc::now_ms() - t1;
+        return depth_scan_bucketed(ref_len, n_refs, ptr.data(), runs, (long)total, max_run_all.load(), max_gap, iv_ref, iv_start, iv_end, iv_sum,
+                                   iv_n, cap, n_intervals, stats);
     });
-    if (stats) stats->extract_ms = sc::now_ms() - t0;
-    const double t1 = sc::now_ms();
-    std::vector<unsigned> ptr((size_t)n_refs + 1, 0);
-    unsigned long long total = 0;
-    for (int r = 0; r < n_refs; r++) { total += per_ref[(size_t)r].size(); if (total > 0xFFFFFFF0ull) return SC_ERR_CAPACITY; ptr[(size_t)r + 1] = (unsigned)total; }
-    sc::PinMem<uint2> pin((size_t)total);
-    uint2* runs = pin.p;
-    for (int r = 0; r < n_refs; r++)
-        if (!per_ref[(size_t)r].empty()) std::memcpy(runs + ptr[(size_t)r], per_ref[(size_t)r].data(), sizeof(uint2) * per_ref[(size_t)r].size());
-    sort_long_refs(ref_len, n_refs, ptr.data(), runs);
-    if (stats) stats->prepare_ms = sc::now_ms() - t1;
-    return depth_scan_bucketed(ref_len, n_refs, ptr.data(), runs, (long)total, max_run_all.load(), max_gap, iv_ref, iv_start, iv_end, iv_sum,
-                               iv_n, cap, n_intervals, stats);
-} catch (const sc::HipError&) {
-    return SC_ERR_HIP;
 }
 
 }  // extern "C"

@@ -1,25 +1,34 @@
-// Host-side plumbing of libstraincall_hip.so: the errors its code throws, and the HIP resources it owns by scope.
+// Host-side plumbing of libstraincall_hip.so: HIPCHK over the errors of sc_error.hpp, the device selection, and the HIP
+// resources it owns by scope.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "../../include/straincall_hip.h"
+#include "sc_error.hpp"
+
 namespace sc {
 
-struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct ScError : std::runtime_error {
-    int code;
-    ScError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
+static_assert(ERR_HIP == SC_ERR_HIP && ERR_INTERNAL == SC_ERR_INTERNAL, "sc_error.hpp restates two codes of the public header");
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw ::sc::HipError(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The one device selection of the library: the calling thread's HIP calls go to `device` from here on.
+inline bool has_device(int device) {
+    int ndev = 0;
+    return hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev;
+}
+inline void select_device(int device) {
+    if (!has_device(device)) throw ScError(SC_ERR_NO_DEVICE, "no HIP device");
+    if (hipSetDevice(device) != hipSuccess) throw ScError(SC_ERR_HIP, "hipSetDevice failed");
 }
 
 // How many device allocations DevBuf and DevMem have made on this thread: a call that wants to report what it had to set

@@ -21,7 +21,7 @@
 #include "sc_ingest.hpp"
 #include "sc_plan.hpp"       // Mt19937
 
-thread_local std::string sc_ingest::tl_error;
+thread_local sc::LastError sc_ingest::tl_error;
 
 struct sc_reads {
     std::vector<int> pos, cigar_off, seq_off, copies, mate_idx, mate_off;
@@ -54,7 +54,7 @@ bool window_depth(const std::vector<const Rec*>& view, int p0, int p1, int& dept
     std::vector<Op> ops;
     depth = 0;
     for (const Rec* r : view) {
-        if (!parse_cigar(r->cigar, r->clen, ops)) { tl_error = "malformed CIGAR"; return false; }
+        if (!parse_cigar(r->cigar, r->clen, ops)) { tl_error.text = "malformed CIGAR"; return false; }
         const int r0 = r->pos, r1 = r0 + md_span(ops) - 1;
         if (p0 <= r0 && p1 > r1) depth += r1 - r0 + 1;
         else if (p0 <= r0 && p1 <= r1) depth += p1 - r0 + 1;
@@ -79,7 +79,7 @@ bool keep_reads(const std::vector<const Rec*>& view, int p0, int p1, int rl, int
         const int rp0 = r->pos, rp1 = rp0 + md_span(ops) - 1;
         crop_to_window(p0, p1, ops, rp0, rp1, cr);
         if (!cr.ok || cr.lead > r->slen || cr.trail > r->quallen) {
-            tl_error = "a read cannot be cropped to the window (soft clips / CIGAR longer than its bases)";
+            tl_error.text = "a read cannot be cropped to the window (soft clips / CIGAR longer than its bases)";
             return false;
         }
         const int cnt = r->slen - cr.lead - cr.trail;
@@ -176,89 +176,93 @@ void mate_table(const std::vector<Kept>& kept, const std::vector<uint32_t>& orde
 extern "C" {
 
 const char* sc_aln_error(sc_aln* a) {
-    if (!tl_error.empty()) return tl_error.c_str();
+    if (!tl_error.text.empty()) return tl_error.text.c_str();
     return a ? a->error.c_str() : "";
 }
 
 int sc_aln_pileup_flags(sc_aln* a, const char* gene, int P, int Q, int mq, unsigned char* covered, unsigned char* has_ins,
                         unsigned char* has_del) {
     if (!a || !gene || Q < P || !covered || !has_ins || !has_del) return SC_ERR_ARG;
-    const int n = Q - P + 1;
-    std::vector<int> diff((size_t)n + 1, 0);
-    memset(has_ins, 0, (size_t)n); memset(has_del, 0, (size_t)n);
-    auto it = a->by_ref.find(gene);
-    if (it != a->by_ref.end()) {
-        auto mark = [&](unsigned char* arr, int p) { if (p >= P && p <= Q) arr[p - P] = 1; };
-        // [p, p + ln) counts towards the coverage; the part of it inside the window as lo..hi (empty: lo > hi)
-        auto cover = [&](int p, int ln, int& lo, int& hi) {
-            lo = std::max(p, P); hi = std::min(p + ln - 1, Q);
-            if (lo <= hi) { diff[(size_t)(lo - P)]++; diff[(size_t)(hi - P + 1)]--; }
-        };
-        std::vector<Op> ops;
-        for (const Rec& r : it->second) {
-            if ((r.flag & 1796) || r.mapq < mq) continue;
-            if (r.ref_end < P || r.pos > Q) continue;
-            // samtools' own CIGAR reading here (= X distinct from M does not matter: all three align bases)
-            ops.clear();
-            for_each_op(r.cigar, r.clen, [&](char op, long len) { if (op != 'H' && op != 'P') ops.push_back({op, (int)len}); });
-            const int mq_char = 33 + std::min(r.mapq, 93);
-            int p = r.pos, lo, hi;
-            bool first = true;
-            for (size_t k = 0; k < ops.size(); k++) {
-                const char op = ops[k].op; const int ln = ops[k].len;
-                if (op == 'M' || op == '=' || op == 'X') {
-                    cover(p, ln, lo, hi);
-                    if (first) {
-                        // '^' + the mapping quality character in front of the first base: '+', '-' and '*' read as indel marks
-                        if (mq_char == '+') mark(has_ins, p);
-                        else if (mq_char == '-' || mq_char == '*') mark(has_del, p);
-                        first = false;
+    return sc::guarded(&tl_error, "sc_aln_pileup_flags", [&] {
+        const int n = Q - P + 1;
+        std::vector<int> diff((size_t)n + 1, 0);
+        memset(has_ins, 0, (size_t)n); memset(has_del, 0, (size_t)n);
+        auto it = a->by_ref.find(gene);
+        if (it != a->by_ref.end()) {
+            auto mark = [&](unsigned char* arr, int p) { if (p >= P && p <= Q) arr[p - P] = 1; };
+            // [p, p + ln) counts towards the coverage; the part of it inside the window as lo..hi (empty: lo > hi)
+            auto cover = [&](int p, int ln, int& lo, int& hi) {
+                lo = std::max(p, P); hi = std::min(p + ln - 1, Q);
+                if (lo <= hi) { diff[(size_t)(lo - P)]++; diff[(size_t)(hi - P + 1)]--; }
+            };
+            std::vector<Op> ops;
+            for (const Rec& r : it->second) {
+                if ((r.flag & 1796) || r.mapq < mq) continue;
+                if (r.ref_end < P || r.pos > Q) continue;
+                // samtools' own CIGAR reading here (= X distinct from M does not matter: all three align bases)
+                ops.clear();
+                for_each_op(r.cigar, r.clen, [&](char op, long len) { if (op != 'H' && op != 'P') ops.push_back({op, (int)len}); });
+                const int mq_char = 33 + std::min(r.mapq, 93);
+                int p = r.pos, lo, hi;
+                bool first = true;
+                for (size_t k = 0; k < ops.size(); k++) {
+                    const char op = ops[k].op; const int ln = ops[k].len;
+                    if (op == 'M' || op == '=' || op == 'X') {
+                        cover(p, ln, lo, hi);
+                        if (first) {
+                            // '^' + the mapping quality character in front of the first base: '+', '-' and '*' read as indel marks
+                            if (mq_char == '+') mark(has_ins, p);
+                            else if (mq_char == '-' || mq_char == '*') mark(has_del, p);
+                            first = false;
+                        }
+                        if (k + 1 < ops.size()) {
+                            if (ops[k + 1].op == 'I') mark(has_ins, p + ln - 1);
+                            else if (ops[k + 1].op == 'D') mark(has_del, p + ln - 1);
+                        }
+                        p += ln;
+                    } else if (op == 'D' || op == 'N') {
+                        // a deleted base prints '*' (read as a deletion mark, StrainCall.cpp:712-735); a reference skip (N)
+                        // prints '>' or '<', which window_adjust does not look for: it only counts towards the coverage
+                        cover(p, ln, lo, hi);
+                        if (op == 'D' && lo <= hi) memset(has_del + (lo - P), 1, (size_t)(hi - lo + 1));
+                        p += ln;
                     }
-                    if (k + 1 < ops.size()) {
-                        if (ops[k + 1].op == 'I') mark(has_ins, p + ln - 1);
-                        else if (ops[k + 1].op == 'D') mark(has_del, p + ln - 1);
-                    }
-                    p += ln;
-                } else if (op == 'D' || op == 'N') {
-                    // a deleted base prints '*' (read as a deletion mark, StrainCall.cpp:712-735); a reference skip (N)
-                    // prints '>' or '<', which window_adjust does not look for: it only counts towards the coverage
-                    cover(p, ln, lo, hi);
-                    if (op == 'D' && lo <= hi) memset(has_del + (lo - P), 1, (size_t)(hi - lo + 1));
-                    p += ln;
                 }
             }
         }
-    }
-    int depth = 0;
-    for (int i = 0; i < n; i++) {
-        depth += diff[(size_t)i];
-        covered[i] = depth > 0;
-        if (!covered[i]) { has_ins[i] = 0; has_del[i] = 0; }
-    }
-    return SC_OK;
+        int depth = 0;
+        for (int i = 0; i < n; i++) {
+            depth += diff[(size_t)i];
+            covered[i] = depth > 0;
+            if (!covered[i]) { has_ins[i] = 0; has_del[i] = 0; }
+        }
+        return SC_OK;
+    });
 }
 
 int sc_aln_load_reads(sc_aln* a, const char* gene, int p0, int p1, int mq, int rl, int max_ins, int max_depth, sc_reads** out) {
     if (!a || !gene || !out) return SC_ERR_ARG;
     *out = nullptr;
     tl_error.clear();
-    std::unique_ptr<sc_reads> R(new sc_reads());
-    const std::vector<const Rec*> view = view_region(*a, gene, p0, p1, mq);
-    R->n_input = (long)view.size();
-    if (!window_depth(view, p0, p1, R->depth)) return SC_ERR_ARG;
-    const double rho = std::min(1.0, (double)max_depth / ((double)R->depth + 0.0));
-    std::vector<Kept> kept;
-    std::string cig_pool;
-    if (!keep_reads(view, p0, p1, rl, max_ins, rho, kept, cig_pool)) return SC_ERR_ARG;
-    // the two sorts run on the rank's ingest threads; SC_INGEST_SORT_MIN: elements worth a thread (tests lower it to reach the merges)
-    const char* e = getenv("SC_INGEST_SORT_MIN");
-    const SortPlan sp{std::min(sc::ingest_threads(), 16), (size_t)std::max(e ? atol(e) : 65536L, 2L)};
-    std::vector<uint32_t> order;
-    std::vector<int> uid_of;
-    collapse_duplicates(kept, cig_pool, sp, *R, order, uid_of);
-    mate_table(kept, order, uid_of, sp, *R);
-    *out = R.release();
-    return SC_OK;
+    return sc::guarded(&tl_error, "sc_aln_load_reads", [&] {
+        std::unique_ptr<sc_reads> R(new sc_reads());
+        const std::vector<const Rec*> view = view_region(*a, gene, p0, p1, mq);
+        R->n_input = (long)view.size();
+        if (!window_depth(view, p0, p1, R->depth)) return SC_ERR_ARG;
+        const double rho = std::min(1.0, (double)max_depth / ((double)R->depth + 0.0));
+        std::vector<Kept> kept;
+        std::string cig_pool;
+        if (!keep_reads(view, p0, p1, rl, max_ins, rho, kept, cig_pool)) return SC_ERR_ARG;
+        // the two sorts run on the rank's ingest threads; SC_INGEST_SORT_MIN: elements worth a thread (tests lower it to reach the merges)
+        const char* e = getenv("SC_INGEST_SORT_MIN");
+        const SortPlan sp{std::min(sc::ingest_threads(), 16), (size_t)std::max(e ? atol(e) : 65536L, 2L)};
+        std::vector<uint32_t> order;
+        std::vector<int> uid_of;
+        collapse_duplicates(kept, cig_pool, sp, *R, order, uid_of);
+        mate_table(kept, order, uid_of, sp, *R);
+        *out = R.release();
+        return SC_OK;
+    });
 }
 
 int sc_reads_get(sc_reads* r, int* n_reads, const int** pos, const char** cigar_text, const int** cigar_off, const char** seq_text,

@@ -13,6 +13,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "sc_error.hpp"
 #include "sc_threads.hpp"
 
 namespace sc_ingest {
@@ -25,7 +26,7 @@ struct Rec {                       // the SAM fields the path reads: 1 2 4 5 6 1
 };
 // The message of the last failing call of THIS thread on any handle (windows are ingested side by side on several
 // threads: a message kept on the shared handle could be another window's); the handle itself keeps what sc_aln_open said.
-extern thread_local std::string tl_error;
+extern thread_local sc::LastError tl_error;
 
 struct Kept {                      // a read that survived the filters, before duplicates collapse
     int relpos; uint32_t cig_off, cig_len; const char* seq; int seq_len; const char* name; int name_len; char suffix;   // suffix: 0, '1' or '2'

@@ -16,7 +16,7 @@
 
 namespace {
 
-thread_local LastError tl_error;
+thread_local sc::LastError tl_error;
 
 // The genes of an index that outlives its calls (sc_profile_index): packed on the host and copied to the device once.
 struct ResidentGenes {
@@ -79,7 +79,7 @@ struct ProfileInput {
         return SC_OK;
     }
 
-    // The lengths checked (SC_ERR_UNSUPPORTED), the device selected (SC_ERR_NO_DEVICE, SC_ERR_HIP); then, unless there is no
+    // The lengths checked (SC_ERR_UNSUPPORTED), the device selected (sc::select_device throws); then, unless there is no
     // segment, the host packing: gene and segment codes, per segment the least passing score (a segment that cannot pass even
     // with every base matched is scored nowhere), and with `seeded` the seed length from the lengths that can pass.  Resident
     // genes were checked and packed when their index was created.
@@ -88,9 +88,7 @@ struct ProfileInput {
         if ((!resident && !gn.rebase(gene_off, n_genes, MAX_COLS, fn.c_str(), "gene", why)) ||
             (n_segs > 0 && !sg.rebase(seg_off, n_segs, MAX_ROWS, fn.c_str(), "segment", why)))
             return tl_error.fail(SC_ERR_UNSUPPORTED, why);
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return tl_error.fail(SC_ERR_NO_DEVICE, "no HIP device");
-        if (hipSetDevice(device) != hipSuccess) return tl_error.fail(SC_ERR_HIP, "hipSetDevice failed");
+        sc::select_device(device);
         if (n_segs == 0) return SC_OK;
         t0 = sc::now_ms();
         if (!resident) pack_genes(gn, gene_text + gene_off[0]);
@@ -263,14 +261,12 @@ int emit_hits(const ProfileInput& in, const std::vector<Cand>& pick, const Trace
     return SC_OK;
 }
 
-// The body of sc_profile_hits and, with `seeded`, of sc_profile_hits_seeded; `fn` names the entry point in messages.  `stats`
-// is the superset both report from.
+// The body of sc_profile_hits and, with `seeded`, of sc_profile_hits_seeded, under the guard; `fn` names the entry point in
+// messages.  `stats` is the superset both report from.
 int profile_hits(const char* fn, int device, const char* gene_text, const long* gene_off, int n_genes, const char* seg_text, const long* seg_off,
                  int n_segs, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, bool seeded, const HitsOut& out,
-                 long* n_hits, sc_profile_seed_stats& stats) try {
+                 long* n_hits, sc_profile_seed_stats& stats) {
     ProfileInput in(fn, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct, max_evalue, ka_lambda, ka_k);
-    tl_error.text.clear();
-    std::memset(&stats, 0, sizeof stats);
     if (n_hits) *n_hits = 0;
     if (const int rc = in.check(out.complete() && n_hits)) return rc;
     if (const int rc = in.prepare(device, seeded); rc != SC_OK || n_segs == 0) return rc;
@@ -327,10 +323,6 @@ int profile_hits(const char* fn, int device, const char* gene_text, const long* 
     }
     stats.total_ms = sc::now_ms() - in.t0;
     return rc;
-} catch (const sc::ScError& e) {
-    return tl_error.fail(e.code, e.what());
-} catch (const sc::HipError&) {
-    return tl_error.fail(SC_ERR_HIP, std::string(fn) + ": a HIP call failed");
 }
 
 }  // namespace
@@ -349,10 +341,13 @@ int sc_profile_hits(int device, const char* gene_text, const long* gene_off, int
                     int n_segs, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, int* hit_seg, int* hit_gene,
                     int* hit_strand, double* hit_score, int* identity, int* align_len, int* qfrom, int* qto, int* hfrom, int* hto,
                     double* evalue, long cap, long* n_hits, sc_profile_stats* stats) {
-    sc_profile_seed_stats all;
-    const int rc = profile_hits("sc_profile_hits", device, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct, max_evalue,
-                                ka_lambda, ka_k, false,
-                                HitsOut{hit_seg, hit_gene, hit_strand, hit_score, identity, align_len, qfrom, qto, hfrom, hto, evalue, cap}, n_hits, all);
+    sc_profile_seed_stats all = {};
+    tl_error.clear();
+    const int rc = sc::guarded(&tl_error, "sc_profile_hits", [&] {
+        return profile_hits("sc_profile_hits", device, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct, max_evalue, ka_lambda,
+                            ka_k, false, HitsOut{hit_seg, hit_gene, hit_strand, hit_score, identity, align_len, qfrom, qto, hfrom, hto, evalue, cap},
+                            n_hits, all);
+    });
     if (stats)
         *stats = sc_profile_stats{all.upload_ms, all.score_ms, all.trace_ms, all.total_ms, all.score_cells,
                                   all.trace_cells, all.n_tiles, all.n_candidates, all.n_traced, all.n_hits};
@@ -363,12 +358,15 @@ int sc_profile_hits_seeded(int device, const char* gene_text, const long* gene_o
                            int n_segs, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, int* hit_seg,
                            int* hit_gene, int* hit_strand, double* hit_score, int* identity, int* align_len, int* qfrom, int* qto,
                            int* hfrom, int* hto, double* evalue, long cap, long* n_hits, sc_profile_seed_stats* stats) {
-    sc_profile_seed_stats all;
-    const int rc = profile_hits("sc_profile_hits_seeded", device, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct,
-                                max_evalue, ka_lambda, ka_k, true,
-                                HitsOut{hit_seg, hit_gene, hit_strand, hit_score, identity, align_len, qfrom, qto, hfrom, hto, evalue, cap}, n_hits, all);
-    if (stats) *stats = all;
-    return rc;
+    sc_profile_seed_stats unasked;
+    sc_profile_seed_stats& all = stats ? *stats : unasked;
+    all = {};
+    tl_error.clear();
+    return sc::guarded(&tl_error, "sc_profile_hits_seeded", [&] {
+        return profile_hits("sc_profile_hits_seeded", device, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct, max_evalue,
+                            ka_lambda, ka_k, true, HitsOut{hit_seg, hit_gene, hit_strand, hit_score, identity, align_len, qfrom, qto, hfrom, hto, evalue, cap},
+                            n_hits, all);
+    });
 }
 
 int sc_profile_seed_length(const int* seg_len, int n_segs, long gene_bases, double min_identity_pct, double max_evalue, double ka_lambda,
@@ -387,42 +385,45 @@ int sc_profile_counts(int device, const char* gene_text, const long* gene_off, i
                       int n_segs, const int* seg_read, int n_reads, double min_identity_pct, double max_evalue, double ka_lambda,
                       double ka_k, int seeded, long cand_room, int* out_gene, int* out_times, int* out_share, long* out_reads, long cap,
                       long* n_out, sc_profile_count_stats* stats) {
-    return profile_counts("sc_profile_counts", device, nullptr, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, seg_read, n_reads,
-                          Samples{nullptr, 0}, min_identity_pct, max_evalue, ka_lambda, ka_k, seeded, cand_room,
-                          RowsOut{nullptr, out_gene, out_times, out_share, out_reads, cap}, n_out, stats, nullptr);
+    tl_error.clear();
+    return sc::guarded(&tl_error, "sc_profile_counts", [&] {
+        return profile_counts("sc_profile_counts", device, nullptr, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, seg_read, n_reads,
+                              Samples{nullptr, 0}, min_identity_pct, max_evalue, ka_lambda, ka_k, seeded, cand_room,
+                              RowsOut{nullptr, out_gene, out_times, out_share, out_reads, cap}, n_out, stats, nullptr);
+    });
 }
 
-int sc_profile_index_create(int device, const char* gene_text, const long* gene_off, int n_genes, sc_profile_index** out) try {
-    const std::string fn = "sc_profile_index_create";
-    tl_error.text.clear();
+int sc_profile_index_create(int device, const char* gene_text, const long* gene_off, int n_genes, sc_profile_index** out) {
+    tl_error.clear();
     if (out) *out = nullptr;
-    if (!out || !gene_text || !gene_off || n_genes < 1) return tl_error.fail(SC_ERR_ARG, fn + ": missing argument");
-    Packed gn;
-    std::string why;
-    if (!gn.rebase(gene_off, n_genes, MAX_COLS, fn.c_str(), "gene", why)) return tl_error.fail(SC_ERR_UNSUPPORTED, why);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return tl_error.fail(SC_ERR_NO_DEVICE, "no HIP device");
-    if (hipSetDevice(device) != hipSuccess) return tl_error.fail(SC_ERR_HIP, "hipSetDevice failed");
-    ProfileInput::pack_genes(gn, gene_text + gene_off[0]);
-    *out = new sc_profile_index(device, std::move(gn));
-    return SC_OK;
-} catch (const sc::HipError&) {
-    return tl_error.fail(SC_ERR_HIP, "sc_profile_index_create: a HIP call failed");
+    return sc::guarded(&tl_error, "sc_profile_index_create", [&] {
+        const std::string fn = "sc_profile_index_create";
+        if (!out || !gene_text || !gene_off || n_genes < 1) return tl_error.fail(SC_ERR_ARG, fn + ": missing argument");
+        Packed gn;
+        std::string why;
+        if (!gn.rebase(gene_off, n_genes, MAX_COLS, fn.c_str(), "gene", why)) return tl_error.fail(SC_ERR_UNSUPPORTED, why);
+        sc::select_device(device);
+        ProfileInput::pack_genes(gn, gene_text + gene_off[0]);
+        *out = new sc_profile_index(device, std::move(gn));
+        return SC_OK;
+    });
 }
 
 int sc_profile_index_info(const sc_profile_index* index, int* n_genes, long* gene_bases, int* n_cached_k, int* cached_k) {
-    if (!index) return tl_error.fail(SC_ERR_ARG, "sc_profile_index_info: missing argument");
-    const Packed& gn = index->res.genes.gn;
-    if (n_genes) *n_genes = (int)gn.off.size() - 1;
-    if (gene_bases) *gene_bases = gn.bytes();
-    int n = 0;
-    for (int k = SEED_MIN_K; k <= SEED_MAX_K; k++) {
-        if (!index->res.seeds[k - SEED_MIN_K]) continue;
-        if (cached_k) cached_k[n] = k;
-        n++;
-    }
-    if (n_cached_k) *n_cached_k = n;
-    return SC_OK;
+    return sc::guarded(&tl_error, "sc_profile_index_info", [&] {
+        if (!index) return tl_error.fail(SC_ERR_ARG, "sc_profile_index_info: missing argument");
+        const Packed& gn = index->res.genes.gn;
+        if (n_genes) *n_genes = (int)gn.off.size() - 1;
+        if (gene_bases) *gene_bases = gn.bytes();
+        int n = 0;
+        for (int k = SEED_MIN_K; k <= SEED_MAX_K; k++) {
+            if (!index->res.seeds[k - SEED_MIN_K]) continue;
+            if (cached_k) cached_k[n] = k;
+            n++;
+        }
+        if (n_cached_k) *n_cached_k = n;
+        return SC_OK;
+    });
 }
 
 int sc_profile_index_counts(sc_profile_index* index, const char* seg_text, const long* seg_off, int n_segs, const int* seg_read, int n_reads,
@@ -432,15 +433,16 @@ int sc_profile_index_counts(sc_profile_index* index, const char* seg_text, const
     sc_profile_cohort_stats unasked;
     sc_profile_cohort_stats& all = stats ? *stats : unasked;
     std::memset(&all, 0, sizeof all);
-    if (!index) return tl_error.fail(SC_ERR_ARG, "sc_profile_index_counts: missing argument");
+    tl_error.clear();
     const long allocs_before = sc::device_allocs;
-    Resident& res = index->res;
-    const int rc = profile_counts("sc_profile_index_counts", res.device, &res, nullptr, nullptr, (int)res.genes.gn.off.size() - 1, seg_text, seg_off,
-                                  n_segs, seg_read, n_reads, Samples{read_sample, n_samples}, min_identity_pct, max_evalue, ka_lambda, ka_k, seeded,
-                                  cand_room, RowsOut{out_sample, out_gene, out_times, out_share, out_reads, cap}, n_out, &all.counts,
-                                  &all.n_index_builds);
-    all.n_samples = n_samples;
-    all.n_allocs = sc::device_allocs - allocs_before;
+    const int rc = sc::guarded(&tl_error, "sc_profile_index_counts", [&] {
+        if (!index) return tl_error.fail(SC_ERR_ARG, "sc_profile_index_counts: missing argument");
+        Resident& res = index->res;
+        return profile_counts("sc_profile_index_counts", res.device, &res, nullptr, nullptr, (int)res.genes.gn.off.size() - 1, seg_text, seg_off, n_segs,
+                              seg_read, n_reads, Samples{read_sample, n_samples}, min_identity_pct, max_evalue, ka_lambda, ka_k, seeded, cand_room,
+                              RowsOut{out_sample, out_gene, out_times, out_share, out_reads, cap}, n_out, &all.counts, &all.n_index_builds);
+    });
+    if (index) { all.n_samples = n_samples; all.n_allocs = sc::device_allocs - allocs_before; }
     return rc;
 }
 

@@ -577,19 +577,18 @@ struct Resident {
 // The samples of a call on an index: read_sample[n_reads], non-decreasing, in 0..n_samples-1
 struct Samples { const int* of_read; int n; };
 
-// The body of sc_profile_counts and sc_profile_index_counts: the front end; once per call the rank table, the stretch plan,
-// the uploads and the index (`res`: the genes are resident, the index of this k is built only when none is cached, and every
+// The body of sc_profile_counts and sc_profile_index_counts, under their guard: the front end; once per call the rank table,
+// the stretch plan, the uploads and the index (`res`: the genes are resident, the index of this k is built only when none is cached, and every
 // array comes from res; *n_index_builds counts the builds); then per stretch the score pass and the stages above; the merge.
 int profile_counts(const char* fn_name, int device, Resident* res, const char* gene_text, const long* gene_off, int n_genes, const char* seg_text,
                    const long* seg_off, int n_segs, const int* seg_read, int n_reads, Samples samples, double min_identity_pct, double max_evalue,
                    double ka_lambda, double ka_k, int seeded, long cand_room, const RowsOut& out, long* n_out, sc_profile_count_stats* stats_out,
-                   int* n_index_builds) try {
+                   int* n_index_builds) {
     ProfileInput in(fn_name, gene_text, gene_off, n_genes, seg_text, seg_off, n_segs, min_identity_pct, max_evalue, ka_lambda, ka_k);
     if (res) in.resident = &res->genes;
     const std::string& fn = in.fn;
     sc_profile_count_stats unasked;
     sc_profile_count_stats& stats = stats_out ? *stats_out : unasked;
-    tl_error.text.clear();
     std::memset(&stats, 0, sizeof stats);
     if (n_out) *n_out = 0;
     if (const int rc = in.check(n_reads >= 0 && (n_segs <= 0 || seg_read) && (!res || out.sample) && out.gene && out.times && out.share &&
@@ -683,10 +682,6 @@ int profile_counts(const char* fn_name, int device, Resident* res, const char* g
     if (n > out.cap) rc = tl_error.fail(SC_ERR_CAPACITY, fn + ": " + std::to_string(n) + " triples, room for " + std::to_string(out.cap));
     stats.total_ms = sc::now_ms() - in.t0;
     return rc;
-} catch (const sc::ScError& e) {
-    return tl_error.fail(e.code, e.what());
-} catch (const sc::HipError&) {
-    return tl_error.fail(SC_ERR_HIP, std::string(fn_name) + ": a HIP call failed");
 }
 
 }  // namespace

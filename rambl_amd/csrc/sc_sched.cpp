@@ -587,11 +587,12 @@ Ctx::~Ctx() {
 // exist or SC_NUMA_BIND=0: nothing is changed then.  sc_ctx_create does the same for the threads and the host memory of the
 // context itself and leaves its caller where it was.
 extern "C" int sc_host_bind(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return 0;
-    cpu_set_t local;
-    const sc::Options opt = sc::read_options();
-    if (opt.off(opt.numa_bind) || !sc::gpu_local_cpus(device, &local)) return 0;
-    if (sched_setaffinity(0, sizeof local, &local) != 0) return 0;
-    return CPU_COUNT(&local);
+    return std::max(0, sc::guarded(nullptr, "sc_host_bind", [&] {        // a failure of any kind is "nothing changed": 0
+        if (!sc::has_device(device)) return 0;
+        cpu_set_t local;
+        const sc::Options opt = sc::read_options();
+        if (opt.off(opt.numa_bind) || !sc::gpu_local_cpus(device, &local)) return 0;
+        if (sched_setaffinity(0, sizeof local, &local) != 0) return 0;
+        return CPU_COUNT(&local);
+    }));
 }

@@ -27,8 +27,7 @@ constexpr int WORDS_BLOCKS = 8192, CELL_BLOCKS = 4096, SCORE_BLOCKS = 8192, PICK
 constexpr long PART_ROOM = 1L << 25;                // (score, genus) records of the chunks held at a time: 256 MiB
 constexpr uint8_t NO_BASE = 4;
 
-thread_local std::string tl_error;
-int fail(int rc, const std::string& msg) { tl_error = msg; return rc; }
+thread_local sc::LastError tl_error;
 
 inline uint8_t taxa_code(char c) {
     switch (c) {
@@ -199,12 +198,6 @@ unsigned grid_of(long units, int own_cap, int grid_cap) {
     return (unsigned)std::max<long>(1, std::min<long>(units, grid_cap > 0 ? grid_cap : own_cap));
 }
 
-void select_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) throw sc::ScError(SC_ERR_NO_DEVICE, "no HIP device");
-    if (hipSetDevice(device) != hipSuccess) throw sc::ScError(SC_ERR_HIP, "hipSetDevice failed");
-}
-
 }  // namespace
 
 // A trained model on one device: the table and n; with keep_counts a copy of m as it stood before it became the table.
@@ -218,207 +211,177 @@ struct sc_taxa_model {
     }
 };
 
-namespace {
-
-int taxa_train(int device, const char* seq_text, const long* seq_off, int n_seqs, const int* seq_genus, int n_genera, int grid_cap, int keep_counts,
-               sc_taxa_model** model, sc_taxa_stats& stats) try {
-    const std::string fn = "sc_taxa_train";
-    if (!model || n_seqs < 0 || grid_cap < 0 || (n_seqs > 0 && (!seq_text || !seq_off || !seq_genus))) return fail(SC_ERR_ARG, fn + ": missing argument");
-    *model = nullptr;
-    if (n_genera < 1 || n_genera > MAX_GENERA)
-        return fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(n_genera) + " genera (1.." + std::to_string(MAX_GENERA) + " supported)");
-    if (n_seqs < 1 || n_seqs > MAX_TRAIN)
-        return fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(n_seqs) + " training sequences (1.." + std::to_string(MAX_TRAIN) + " supported)");
-    const double t0 = sc::now_ms();
-    if (seq_off[n_seqs] - seq_off[0] > MAX_TRAIN_BASES)
-        return fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(seq_off[n_seqs] - seq_off[0]) + " training bases in all (at most " +
-                                            std::to_string(MAX_TRAIN_BASES) + " supported)");
-    std::vector<long> off((size_t)n_seqs + 1);
-    std::vector<int> genus(seq_genus, seq_genus + n_seqs), genus_seqs((size_t)n_genera, 0);
-    for (int s = 0; s <= n_seqs; s++) off[(size_t)s] = seq_off[s] - seq_off[0];
-    for (int s = 0; s < n_seqs; s++) {
-        const long len = off[(size_t)s + 1] - off[(size_t)s];
-        if (len < 0 || len > MAX_TRAIN_LEN)
-            return fail(SC_ERR_UNSUPPORTED, fn + ": training sequence " + std::to_string(s) + " has " + std::to_string(len) + " bases (0.." +
-                                                std::to_string(MAX_TRAIN_LEN) + " supported)");
-        if (genus[(size_t)s] < 0 || genus[(size_t)s] >= n_genera)
-            return fail(SC_ERR_UNSUPPORTED, fn + ": training sequence " + std::to_string(s) + " has genus " + std::to_string(genus[(size_t)s]) +
-                                                " (0.." + std::to_string(n_genera - 1) + " supported)");
-        genus_seqs[(size_t)genus[(size_t)s]]++;
-    }
-    std::vector<uint8_t> codes((size_t)off.back());
-    for (size_t k = 0; k < codes.size(); k++) codes[k] = taxa_code(seq_text[seq_off[0] + (long)k]);
-    select_device(device);
-    std::unique_ptr<sc_taxa_model> mo(new sc_taxa_model(device, n_genera, keep_counts != 0));
-    sc::DevMem<uint8_t> d_codes(codes.size());
-    sc::DevMem<long> d_off(off.size());
-    sc::DevMem<int> d_genus(genus.size()), d_genus_seqs((size_t)n_genera);
-    const size_t table_bytes = (size_t)N_WORDS * (size_t)n_genera * sizeof(int);
-    sc::TimedStream st;
-    st.mark("upload");
-    st.h2d(d_codes, codes); st.h2d(d_off, off); st.h2d(d_genus, genus); st.h2d(d_genus_seqs, genus_seqs);
-    st.zero(mo->table.p, table_bytes);
-    st.zero(mo->n.p, N_WORDS * sizeof(unsigned));
-    st.mark("words");
-    hipLaunchKernelGGL(k_taxa_words, dim3(grid_of(n_seqs, WORDS_BLOCKS, grid_cap)), dim3(64), 0, st, d_codes.p, d_off.p, d_genus.p, n_seqs, n_genera,
-                       (unsigned*)mo->table.p, mo->n.p);
-    st.launched();
-    if (mo->m) HIPCHK(hipMemcpyAsync(mo->m->p, mo->table.p, table_bytes, hipMemcpyDeviceToDevice, st));
-    st.mark("table");
-    hipLaunchKernelGGL(k_taxa_table, dim3(grid_of(((long)N_WORDS * n_genera + 255) / 256, CELL_BLOCKS, grid_cap)), dim3(256), 0, st, mo->table.p, mo->n.p,
-                       d_genus_seqs.p, n_genera, n_seqs);
-    st.launched();
-    st.mark("done");
-    std::vector<unsigned> n_host(N_WORDS);
-    st.d2h(n_host, mo->n);
-    st.sync();
-    stats.upload_ms = st.ms("upload", "words"); stats.words_ms = st.ms("words", "table"); stats.table_ms = st.ms("table", "done");
-    stats.n_seqs = n_seqs; stats.n_genera = n_genera; stats.table_bytes = (long)table_bytes;
-    for (unsigned v : n_host) stats.n_words += v;
-    stats.total_ms = sc::now_ms() - t0;
-    *model = mo.release();
-    return SC_OK;
-} catch (const sc::ScError& e) {
-    return fail(e.code, e.what());
-} catch (const sc::HipError& e) {
-    return fail(SC_ERR_HIP, std::string("sc_taxa_train: a HIP call failed: ") + e.what());
-} catch (const std::exception& e) {
-    return fail(SC_ERR_INTERNAL, std::string("sc_taxa_train: ") + e.what());
-}
-
-int taxa_classify(const sc_taxa_model* mo, const char* query_text, const long* query_off, int n_queries, const unsigned long long* query_key,
-                  unsigned long long seed, int n_trials, int grid_cap, int* best_genus, int* trial_winner, int* n_words, sc_taxa_stats& stats) try {
-    const std::string fn = "sc_taxa_classify";
-    if (!mo || n_queries < 0 || grid_cap < 0 || (n_queries > 0 && (!query_text || !query_off || !query_key || !best_genus || !trial_winner || !n_words)))
-        return fail(SC_ERR_ARG, fn + ": missing argument");
-    if (n_trials < 1 || n_trials > MAX_TRIALS)
-        return fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(n_trials) + " trials (1.." + std::to_string(MAX_TRIALS) + " supported)");
-    for (int r = 0; r < n_queries; r++) {
-        const long len = query_off[r + 1] - query_off[r];
-        if (len < 1 || len > MAX_QUERY)
-            return fail(SC_ERR_UNSUPPORTED, fn + ": query " + std::to_string(r) + " has " + std::to_string(len) + " bases (1.." + std::to_string(MAX_QUERY) +
-                                                " supported)");
-    }
-    if (n_queries == 0) return SC_OK;
-    const double t0 = sc::now_ms();
-    // the word lists: every window of ACGTU bases, in order
-    std::vector<uint16_t> words;
-    std::vector<long> word_off((size_t)n_queries + 1, 0);
-    words.reserve((size_t)(query_off[n_queries] - query_off[0]));
-    for (int r = 0; r < n_queries; r++) {
-        unsigned fw = 0;
-        int run = 0;
-        for (long i = query_off[r]; i < query_off[r + 1]; i++) {
-            const uint8_t c = taxa_code(query_text[i]);
-            if (c == NO_BASE) { run = 0; continue; }
-            fw = ((fw << 2) | c) & (unsigned)(N_WORDS - 1);
-            if (++run >= TAXA_K) words.push_back((uint16_t)fw);
-        }
-        word_off[(size_t)r + 1] = (long)words.size();
-        n_words[r] = (int)(word_off[(size_t)r + 1] - word_off[(size_t)r]);
-    }
-    select_device(mo->device);
-    const int n_chunks = (mo->G + CHUNK - 1) / CHUNK, slots = 1 + n_trials;
-    const int batch = (int)std::max<long>(1, std::min<long>(n_queries, PART_ROOM / ((long)n_chunks * slots)));   // queries whose records are held at a time
-    sc::DevMem<uint16_t> d_words(words.size());
-    sc::DevMem<long> d_word_off(word_off.size());
-    sc::DevMem<unsigned long long> d_key((size_t)n_queries);
-    sc::DevMem<int> d_best((size_t)n_queries), d_winner((size_t)n_queries * (size_t)n_trials);
-    sc::DevMem<Best> d_part((size_t)batch * (size_t)n_chunks * (size_t)slots);
-    sc::TimedStream st;
-    st.mark("upload");
-    st.h2d(d_words, words); st.h2d(d_word_off, word_off);
-    st.h2d(d_key.p, query_key, (size_t)n_queries * sizeof(unsigned long long));
-    st.mark("score");
-    for (int q0 = 0; q0 < n_queries; q0 += batch) {
-        const int nq = std::min(batch, n_queries - q0);
-        hipLaunchKernelGGL(k_taxa_score, dim3(grid_of((long)nq * n_chunks, SCORE_BLOCKS, grid_cap)), dim3(64 * SCORE_WAVES), 0, st, mo->table.p, mo->G,
-                           n_chunks, d_words.p, d_word_off.p, d_key.p, q0, nq, seed, n_trials, d_part.p);
-        st.launched();
-        hipLaunchKernelGGL(k_taxa_pick, dim3(grid_of(((long)nq * slots + 255) / 256, PICK_BLOCKS, grid_cap)), dim3(256), 0, st, d_part.p, n_chunks,
-                           d_word_off.p, q0, nq, n_trials, d_best.p, d_winner.p);
-        st.launched();
-    }
-    st.mark("scored");
-    st.d2h(best_genus, d_best.p, (size_t)n_queries * sizeof(int));
-    st.d2h(trial_winner, d_winner.p, (size_t)n_queries * (size_t)n_trials * sizeof(int));
-    st.sync();
-    stats.upload_ms = st.ms("upload", "score"); stats.score_ms = st.ms("score", "scored");
-    stats.n_seqs = n_queries; stats.n_words = (long)words.size(); stats.n_genera = mo->G;
-    stats.table_bytes = (long)((size_t)N_WORDS * (size_t)mo->G * sizeof(int));
-    stats.total_ms = sc::now_ms() - t0;
-    return SC_OK;
-} catch (const sc::ScError& e) {
-    return fail(e.code, e.what());
-} catch (const sc::HipError& e) {
-    return fail(SC_ERR_HIP, std::string("sc_taxa_classify: a HIP call failed: ") + e.what());
-} catch (const std::exception& e) {
-    return fail(SC_ERR_INTERNAL, std::string("sc_taxa_classify: ") + e.what());
-}
-
-}  // namespace
-
 extern "C" {
 
-const char* sc_taxa_error(void) { return tl_error.c_str(); }
+const char* sc_taxa_error(void) { return tl_error.text.c_str(); }
 
 int sc_taxa_train(int device, const char* seq_text, const long* seq_off, int n_seqs, const int* seq_genus, int n_genera, int grid_cap,
-                  int keep_counts, sc_taxa_model** model, sc_taxa_stats* stats) {
-    sc_taxa_stats all = {};
+                  int keep_counts, sc_taxa_model** model, sc_taxa_stats* stats_out) {
+    sc_taxa_stats unasked;
+    sc_taxa_stats& stats = stats_out ? *stats_out : unasked;
+    stats = {};
     tl_error.clear();
-    const int rc = taxa_train(device, seq_text, seq_off, n_seqs, seq_genus, n_genera, grid_cap, keep_counts, model, all);
-    if (stats) *stats = all;
-    return rc;
+    return sc::guarded(&tl_error, "sc_taxa_train", [&] {
+        const std::string fn = "sc_taxa_train";
+        if (!model || n_seqs < 0 || grid_cap < 0 || (n_seqs > 0 && (!seq_text || !seq_off || !seq_genus))) return tl_error.fail(SC_ERR_ARG, fn + ": missing argument");
+        *model = nullptr;
+        if (n_genera < 1 || n_genera > MAX_GENERA)
+            return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(n_genera) + " genera (1.." + std::to_string(MAX_GENERA) + " supported)");
+        if (n_seqs < 1 || n_seqs > MAX_TRAIN)
+            return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(n_seqs) + " training sequences (1.." + std::to_string(MAX_TRAIN) + " supported)");
+        const double t0 = sc::now_ms();
+        if (seq_off[n_seqs] - seq_off[0] > MAX_TRAIN_BASES)
+            return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(seq_off[n_seqs] - seq_off[0]) + " training bases in all (at most " +
+                                                         std::to_string(MAX_TRAIN_BASES) + " supported)");
+        std::vector<long> off((size_t)n_seqs + 1);
+        std::vector<int> genus(seq_genus, seq_genus + n_seqs), genus_seqs((size_t)n_genera, 0);
+        for (int s = 0; s <= n_seqs; s++) off[(size_t)s] = seq_off[s] - seq_off[0];
+        for (int s = 0; s < n_seqs; s++) {
+            const long len = off[(size_t)s + 1] - off[(size_t)s];
+            if (len < 0 || len > MAX_TRAIN_LEN)
+                return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": training sequence " + std::to_string(s) + " has " + std::to_string(len) + " bases (0.." +
+                                                             std::to_string(MAX_TRAIN_LEN) + " supported)");
+            if (genus[(size_t)s] < 0 || genus[(size_t)s] >= n_genera)
+                return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": training sequence " + std::to_string(s) + " has genus " + std::to_string(genus[(size_t)s]) +
+                                                             " (0.." + std::to_string(n_genera - 1) + " supported)");
+            genus_seqs[(size_t)genus[(size_t)s]]++;
+        }
+        std::vector<uint8_t> codes((size_t)off.back());
+        for (size_t k = 0; k < codes.size(); k++) codes[k] = taxa_code(seq_text[seq_off[0] + (long)k]);
+        sc::select_device(device);
+        std::unique_ptr<sc_taxa_model> mo(new sc_taxa_model(device, n_genera, keep_counts != 0));
+        sc::DevMem<uint8_t> d_codes(codes.size());
+        sc::DevMem<long> d_off(off.size());
+        sc::DevMem<int> d_genus(genus.size()), d_genus_seqs((size_t)n_genera);
+        const size_t table_bytes = (size_t)N_WORDS * (size_t)n_genera * sizeof(int);
+        sc::TimedStream st;
+        st.mark("upload");
+        st.h2d(d_codes, codes); st.h2d(d_off, off); st.h2d(d_genus, genus); st.h2d(d_genus_seqs, genus_seqs);
+        st.zero(mo->table.p, table_bytes);
+        st.zero(mo->n.p, N_WORDS * sizeof(unsigned));
+        st.mark("words");
+        hipLaunchKernelGGL(k_taxa_words, dim3(grid_of(n_seqs, WORDS_BLOCKS, grid_cap)), dim3(64), 0, st, d_codes.p, d_off.p, d_genus.p, n_seqs, n_genera,
+                           (unsigned*)mo->table.p, mo->n.p);
+        st.launched();
+        if (mo->m) HIPCHK(hipMemcpyAsync(mo->m->p, mo->table.p, table_bytes, hipMemcpyDeviceToDevice, st));
+        st.mark("table");
+        hipLaunchKernelGGL(k_taxa_table, dim3(grid_of(((long)N_WORDS * n_genera + 255) / 256, CELL_BLOCKS, grid_cap)), dim3(256), 0, st, mo->table.p, mo->n.p,
+                           d_genus_seqs.p, n_genera, n_seqs);
+        st.launched();
+        st.mark("done");
+        std::vector<unsigned> n_host(N_WORDS);
+        st.d2h(n_host, mo->n);
+        st.sync();
+        stats.upload_ms = st.ms("upload", "words"); stats.words_ms = st.ms("words", "table"); stats.table_ms = st.ms("table", "done");
+        stats.n_seqs = n_seqs; stats.n_genera = n_genera; stats.table_bytes = (long)table_bytes;
+        for (unsigned v : n_host) stats.n_words += v;
+        stats.total_ms = sc::now_ms() - t0;
+        *model = mo.release();
+        return SC_OK;
+    });
 }
 
-int sc_taxa_classify(const sc_taxa_model* model, const char* query_text, const long* query_off, int n_queries,
-                     const unsigned long long* query_key, unsigned long long seed, int n_trials, int grid_cap, int* best_genus,
-                     int* trial_winner, int* n_words, sc_taxa_stats* stats) {
-    sc_taxa_stats all = {};
+int sc_taxa_classify(const sc_taxa_model* mo, const char* query_text, const long* query_off, int n_queries, const unsigned long long* query_key,
+                     unsigned long long seed, int n_trials, int grid_cap, int* best_genus, int* trial_winner, int* n_words,
+                     sc_taxa_stats* stats_out) {
+    sc_taxa_stats unasked;
+    sc_taxa_stats& stats = stats_out ? *stats_out : unasked;
+    stats = {};
     tl_error.clear();
-    const int rc = taxa_classify(model, query_text, query_off, n_queries, query_key, seed, n_trials, grid_cap, best_genus, trial_winner, n_words, all);
-    if (stats) *stats = all;
-    return rc;
+    return sc::guarded(&tl_error, "sc_taxa_classify", [&] {
+        const std::string fn = "sc_taxa_classify";
+        if (!mo || n_queries < 0 || grid_cap < 0 || (n_queries > 0 && (!query_text || !query_off || !query_key || !best_genus || !trial_winner || !n_words)))
+            return tl_error.fail(SC_ERR_ARG, fn + ": missing argument");
+        if (n_trials < 1 || n_trials > MAX_TRIALS)
+            return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": " + std::to_string(n_trials) + " trials (1.." + std::to_string(MAX_TRIALS) + " supported)");
+        for (int r = 0; r < n_queries; r++) {
+            const long len = query_off[r + 1] - query_off[r];
+            if (len < 1 || len > MAX_QUERY)
+                return tl_error.fail(SC_ERR_UNSUPPORTED, fn + ": query " + std::to_string(r) + " has " + std::to_string(len) + " bases (1.." + std::to_string(MAX_QUERY) +
+                                                             " supported)");
+        }
+        if (n_queries == 0) return SC_OK;
+        const double t0 = sc::now_ms();
+        // the word lists: every window of ACGTU bases, in order
+        std::vector<uint16_t> words;
+        std::vector<long> word_off((size_t)n_queries + 1, 0);
+        words.reserve((size_t)(query_off[n_queries] - query_off[0]));
+        for (int r = 0; r < n_queries; r++) {
+            unsigned fw = 0;
+            int run = 0;
+            for (long i = query_off[r]; i < query_off[r + 1]; i++) {
+                const uint8_t c = taxa_code(query_text[i]);
+                if (c == NO_BASE) { run = 0; continue; }
+                fw = ((fw << 2) | c) & (unsigned)(N_WORDS - 1);
+                if (++run >= TAXA_K) words.push_back((uint16_t)fw);
+            }
+            word_off[(size_t)r + 1] = (long)words.size();
+            n_words[r] = (int)(word_off[(size_t)r + 1] - word_off[(size_t)r]);
+        }
+        sc::select_device(mo->device);
+        const int n_chunks = (mo->G + CHUNK - 1) / CHUNK, slots = 1 + n_trials;
+        const int batch = (int)std::max<long>(1, std::min<long>(n_queries, PART_ROOM / ((long)n_chunks * slots)));   // queries whose records are held at a time
+        sc::DevMem<uint16_t> d_words(words.size());
+        sc::DevMem<long> d_word_off(word_off.size());
+        sc::DevMem<unsigned long long> d_key((size_t)n_queries);
+        sc::DevMem<int> d_best((size_t)n_queries), d_winner((size_t)n_queries * (size_t)n_trials);
+        sc::DevMem<Best> d_part((size_t)batch * (size_t)n_chunks * (size_t)slots);
+        sc::TimedStream st;
+        st.mark("upload");
+        st.h2d(d_words, words); st.h2d(d_word_off, word_off);
+        st.h2d(d_key.p, query_key, (size_t)n_queries * sizeof(unsigned long long));
+        st.mark("score");
+        for (int q0 = 0; q0 < n_queries; q0 += batch) {
+            const int nq = std::min(batch, n_queries - q0);
+            hipLaunchKernelGGL(k_taxa_score, dim3(grid_of((long)nq * n_chunks, SCORE_BLOCKS, grid_cap)), dim3(64 * SCORE_WAVES), 0, st, mo->table.p, mo->G,
+                               n_chunks, d_words.p, d_word_off.p, d_key.p, q0, nq, seed, n_trials, d_part.p);
+            st.launched();
+            hipLaunchKernelGGL(k_taxa_pick, dim3(grid_of(((long)nq * slots + 255) / 256, PICK_BLOCKS, grid_cap)), dim3(256), 0, st, d_part.p, n_chunks,
+                               d_word_off.p, q0, nq, n_trials, d_best.p, d_winner.p);
+            st.launched();
+        }
+        st.mark("scored");
+        st.d2h(best_genus, d_best.p, (size_t)n_queries * sizeof(int));
+        st.d2h(trial_winner, d_winner.p, (size_t)n_queries * (size_t)n_trials * sizeof(int));
+        st.sync();
+        stats.upload_ms = st.ms("upload", "score"); stats.score_ms = st.ms("score", "scored");
+        stats.n_seqs = n_queries; stats.n_words = (long)words.size(); stats.n_genera = mo->G;
+        stats.table_bytes = (long)((size_t)N_WORDS * (size_t)mo->G * sizeof(int));
+        stats.total_ms = sc::now_ms() - t0;
+        return SC_OK;
+    });
 }
 
-int sc_taxa_model_counts(const sc_taxa_model* mo, int genus, unsigned* m_out, unsigned* n_out) try {
+int sc_taxa_model_counts(const sc_taxa_model* mo, int genus, unsigned* m_out, unsigned* n_out) {
     tl_error.clear();
-    if (!mo || !m_out || !n_out || genus < 0 || genus >= mo->G) return fail(SC_ERR_ARG, "sc_taxa_model_counts: missing argument or no such genus");
-    if (!mo->m) return fail(SC_ERR_UNSUPPORTED, "sc_taxa_model_counts: the counts became the table in place; train with keep_counts to read them back");
-    select_device(mo->device);
-    sc::DevMem<unsigned> d_m(N_WORDS);
-    sc::TimedStream st;
-    hipLaunchKernelGGL(k_taxa_column, dim3(N_WORDS / 256), dim3(256), 0, st, (const int*)mo->m->p, mo->G, genus, (int*)d_m.p);
-    st.launched();
-    st.d2h(m_out, d_m.p, N_WORDS * sizeof(unsigned));
-    st.d2h(n_out, mo->n.p, N_WORDS * sizeof(unsigned));
-    st.sync();
-    return SC_OK;
-} catch (const sc::ScError& e) {
-    return fail(e.code, e.what());
-} catch (const sc::HipError& e) {
-    return fail(SC_ERR_HIP, std::string("sc_taxa_model_counts: a HIP call failed: ") + e.what());
-} catch (const std::exception& e) {
-    return fail(SC_ERR_INTERNAL, std::string("sc_taxa_model_counts: ") + e.what());
+    return sc::guarded(&tl_error, "sc_taxa_model_counts", [&] {
+        if (!mo || !m_out || !n_out || genus < 0 || genus >= mo->G) return tl_error.fail(SC_ERR_ARG, "sc_taxa_model_counts: missing argument or no such genus");
+        if (!mo->m) return tl_error.fail(SC_ERR_UNSUPPORTED, "sc_taxa_model_counts: the counts became the table in place; train with keep_counts to read them back");
+        sc::select_device(mo->device);
+        sc::DevMem<unsigned> d_m(N_WORDS);
+        sc::TimedStream st;
+        hipLaunchKernelGGL(k_taxa_column, dim3(N_WORDS / 256), dim3(256), 0, st, (const int*)mo->m->p, mo->G, genus, (int*)d_m.p);
+        st.launched();
+        st.d2h(m_out, d_m.p, N_WORDS * sizeof(unsigned));
+        st.d2h(n_out, mo->n.p, N_WORDS * sizeof(unsigned));
+        st.sync();
+        return SC_OK;
+    });
 }
 
-int sc_taxa_model_table(const sc_taxa_model* mo, int genus, int* q_out) try {
+int sc_taxa_model_table(const sc_taxa_model* mo, int genus, int* q_out) {
     tl_error.clear();
-    if (!mo || !q_out || genus < 0 || genus >= mo->G) return fail(SC_ERR_ARG, "sc_taxa_model_table: missing argument or no such genus");
-    select_device(mo->device);
-    sc::DevMem<int> d_q(N_WORDS);
-    sc::TimedStream st;
-    hipLaunchKernelGGL(k_taxa_column, dim3(N_WORDS / 256), dim3(256), 0, st, mo->table.p, mo->G, genus, d_q.p);
-    st.launched();
-    st.d2h(q_out, d_q.p, N_WORDS * sizeof(int));
-    st.sync();
-    return SC_OK;
-} catch (const sc::ScError& e) {
-    return fail(e.code, e.what());
-} catch (const sc::HipError& e) {
-    return fail(SC_ERR_HIP, std::string("sc_taxa_model_table: a HIP call failed: ") + e.what());
-} catch (const std::exception& e) {
-    return fail(SC_ERR_INTERNAL, std::string("sc_taxa_model_table: ") + e.what());
+    return sc::guarded(&tl_error, "sc_taxa_model_table", [&] {
+        if (!mo || !q_out || genus < 0 || genus >= mo->G) return tl_error.fail(SC_ERR_ARG, "sc_taxa_model_table: missing argument or no such genus");
+        sc::select_device(mo->device);
+        sc::DevMem<int> d_q(N_WORDS);
+        sc::TimedStream st;
+        hipLaunchKernelGGL(k_taxa_column, dim3(N_WORDS / 256), dim3(256), 0, st, mo->table.p, mo->G, genus, d_q.p);
+        st.launched();
+        st.d2h(q_out, d_q.p, N_WORDS * sizeof(int));
+        st.sync();
+        return SC_OK;
+    });
 }
 
 void sc_taxa_free(sc_taxa_model* model) {

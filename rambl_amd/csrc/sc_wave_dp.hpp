@@ -230,12 +230,6 @@ inline int code_of(char c) {
     }
 }
 
-// The last error of a family's entry point on this thread.
-struct LastError {
-    std::string text;
-    int fail(int rc, const std::string& msg) { text = msg; return rc; }
-};
-
 // The sequences of one side of a call, off[n + 1] into a text: rebase() checks every length and moves the offsets to start
 // at 0, pack() turns the text into one code byte per base.
 struct Packed {
