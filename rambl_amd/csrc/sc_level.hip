@@ -480,7 +480,10 @@ __device__ __forceinline__ void level_sample_body(const IT& it, unsigned char* s
         if (!STAY) return;                                 // a finished wavefront no longer counts at the barriers below
         urn_chain_shadow<NW>(h, l.s_x);                    // ... one that has to stay takes part in them
     } else {
-        urn_chain_q<NB, ROWS_LDS, NW>(job, h, l.s_sp, R, l.s_slot, l.s_a, l.s_p, l.s_kf, l.s_a0f, l.s_x, s_uwin, s_rows, stride, tid);
+        auto chain = [&](auto wide_q) __attribute__((always_inline)) {
+            urn_chain_q<NB, ROWS_LDS, NW, decltype(wide_q)::value>(job, h, l.s_sp, R, l.s_slot, l.s_a, l.s_p, l.s_kf, l.s_a0f, l.s_x, s_uwin, s_rows, stride, tid);
+        };
+        if (Q >= 16 * NW) chain(std::true_type{}); else chain(std::false_type{});     // (uniform: one of two instances of the same pass loop)
     }
     if (!STAY) nt = 64 * NW;
     draw_log_counts(job, h, l.s_cnt, tid, nt);               // (behind the chain's closing barrier, by every wavefront still here)

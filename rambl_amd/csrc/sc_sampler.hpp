@@ -7,6 +7,7 @@
 // the reference's formula, so every draw equals the reference's draw.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 
@@ -220,16 +221,19 @@ constexpr int UWIN = 1024;     // uniforms staged in LDS (fp32), refilled in hal
 // (ro, upos, uniform refill), [4] second barrier, [5] passes, and the rest of the commit section: [6] issue_loads, [7] the
 // s_kf commit, [8] the draw-log store.  The three stamps inside the commit section first wait for the LDS operations in
 // front of them (CHAIN_STAMP_W): what is asynchronous in the product build -- the next rows' LDS reads, the atomic -- is
-// charged to its own part here, so the parts add up to more than the section costs when they overlap.
+// charged to its own part here, so the parts add up to more than the section costs when they overlap.  The last pass of a
+// level runs the commit section and its stamps like any other and leaves in front of the second barrier and its stamp.
 __device__ unsigned long long g_chain_prof[12];
-#define CHAIN_STAMP(k) do { if (wv == 0) { const unsigned long long t_ = clock64(); prof[k] += t_ - tprev; tprev = t_; } } while (0)
+#define CHAIN_STAMP(k) do { if (wv == 0) { const unsigned t_ = (unsigned)clock64(); prof[k] += t_ - tprev; tprev = t_; } } while (0)
 #define CHAIN_STAMP_W(k) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); CHAIN_STAMP(k); } while (0)
 #else
 #define CHAIN_STAMP(k) do {} while (0)
 #define CHAIN_STAMP_W(k) do {} while (0)
 #endif
 
-template <int NQ, bool ROWS_LDS, int NW, class JD>
+// WIDE_Q: the level has at least a window of draw slots (Q >= 16 * NW), so a pass moves a lane's row at most once past the
+// last one.  The caller decides it once per level (the pass loop holds neither the test nor the other way's code).
+template <int NQ, bool ROWS_LDS, int NW, bool WIDE_Q, class JD>
 __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, const StrainParam* s_sp, LevelResult* __restrict__ R,
                                             const int* s_slot, volatile double* s_a, volatile double* s_p, unsigned* s_kf,
                                             const float* s_a0f, int* s_x, float* s_uwin, const float* rows_lds, int stride, int tid) {
@@ -261,12 +265,15 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
     f4v a0q[NQ];
 #pragma unroll
     for (int g = 0; g < NQ; g++) a0q[g] = *(const f4v*)(s_a0f + cbase + 4 * g);
-    unsigned long long n_exact = 0, n_slow = 0, n_pass = 0;
+    unsigned n_exact = 0, n_slow = 0, n_pass = 0;           // (a level has at most MAX_DRAWS draws: 32 bits, widened in LevelResult)
     const unsigned long long clk0 = clock64(), wall0 = wall_clock64();
 
-    // uniforms: draws [ulo, ulo + UWIN) live in s_uwin[p & (UWIN-1)]; wave 0 refills
+    // uniforms: draws [ulo, ulo + UWIN) live in s_uwin[p & (UWIN-1)]; wave 0 refills.  unext is the next t at which it
+    // has anything to do: ulo + UWIN / 4 (prefetch the next half window into ux0 / ux1) and ulo + UWIN / 2 (swap it in)
+    // in turn, every quarter of a window.  The other wavefronts never get there, so a pass asks one question, not who
+    // and which.
     int ulo = 0;
-    bool upf = false;
+    int unext = wv == 0 ? UWIN / 4 : INT_MAX;
     f4v ux0 = 0.0f, ux1 = 0.0f;
     if (wv == 0) {
 #pragma unroll
@@ -288,10 +295,13 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
     };
     if (total > 0) issue_loads();
 #ifdef SC_CHAIN_PROF
-    unsigned long long prof[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = clock64();
+    unsigned prof[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = (unsigned)clock64();     // (32 bits hold a level's cycles: scalar registers are short in this loop)
 #endif
+    // Every pass ends with the same commit, the last one too, and the loop is left behind that commit and in front of
+    // the pass's second barrier -- where the last pass has always left it.  The barriers of the chain are therefore what
+    // urn_chain_shadow takes part in: one behind the staged uniforms, two per pass but one in the last, one behind the loop.
 #pragma unroll 1
-    while (t < total) {
+    while (total > 0) {
         asm volatile("" ::: "memory");                      // s_kf below must be re-read
         n_pass++;
         // this lane's quarter: cumulative weights with the counts in front of draw t
@@ -349,8 +359,13 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
         const float lim_up = fmaf(uf + 0x1p-22f, posf, epsT);
         const float lim_dn = fmaf((1.0f + 0x1p-22f) - uf, posf, epsT);
         // NaN (flagged slot) and T == 0 fail the test
-        const bool okl = (__uint_as_float(dn) >= lim_dn) && ((__uint_as_float(up) >= lim_up) || (alt >= lim_dn));
-        const unsigned long long F = ~__ballot(okl);
+        // (a ballot per compare and the masks joined as scalars: no branch around the second and third compare -- behind
+        // which the compiler had moved the LDS read of klast -- and no 0 / 1 per lane to take the ballot from; every lane
+        // of the wavefront is active here)
+        const unsigned long long ok_dn = __builtin_amdgcn_ballot_w64(__uint_as_float(dn) >= lim_dn);
+        const unsigned long long ok_up = __builtin_amdgcn_ballot_w64(__uint_as_float(up) >= lim_up);
+        const unsigned long long ok_alt = __builtin_amdgcn_ballot_w64(alt >= lim_dn);
+        const unsigned long long F = ~(ok_dn & (ok_up | ok_alt));
         const int fpos = F ? 16 * wv + ((int)__builtin_ctzll(F) >> 2) : 16 * NW;
         if (lane == 0) s_x[wv] = fpos;
         int c = __popc(w);
@@ -384,13 +399,15 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
             adv = 1;
         }
         const bool acc = (pos < adv) && (k == 0);
-        SC_GLOBAL unsigned char* const lg = dlog + (t + pos);     // acc: t + pos < total <= JobDev::dlog_cap
+        const unsigned lg = (unsigned)(t + pos);                 // acc: t + pos < total <= JobDev::dlog_cap (the log: base + 32 bits)
         t += adv;
-        if (t >= total) {
-            if (acc) { __hip_atomic_fetch_add(&s_kf[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); *lg = (unsigned char)c; }
-            break;
-        }
-        if (Q >= 16 * NW) {
+        // The row and the uniform of this lane's draw in the next window.  The last pass (t == total) moves them like any
+        // other and loads what nobody uses, from inside the rows and the staged uniforms: ro stays below wrap (WIDE_Q:
+        // ro < wrap and adv * stride <= 16 * NW * stride <= wrap, so r1 < 2 * wrap and the smaller of r1, r1 - wrap is
+        // < wrap; else a row index mod Q), the lane reads ro .. ro + SP - 1 <= the 16 zeros behind the last row, and upos
+        // is masked to the window.  A refill in the last pass reads uniforms below total + 1280, inside the stream's
+        // padding of 2048, and stores them to the half of s_uwin no draw of this level reads any more.
+        if (WIDE_Q) {
             const unsigned r1 = (unsigned)(ro + adv * stride);
             const unsigned r2 = r1 - (unsigned)wrap;         // wraps to a huge value while r1 < wrap
             ro = (int)(r1 < r2 ? r1 : r2);
@@ -398,19 +415,21 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
             ro = ((ro / stride + adv) % Q) * stride;
         }
         upos = (upos + adv) & (UWIN - 1);
-        // uniforms: prefetch the next half window, swap it in when the window has moved past the old one
-        if (wv == 0) {
-            if (!upf && t >= ulo + UWIN / 4) {
+        // uniforms: prefetch the next half window, swap it in when the window has moved past the old one.  (A pass moves
+        // t by at most 128 and the two are 256 apart, so they take turns.  Two tests in a row, not if / else: around an
+        // else the compiler loads into other registers and copies them to ux0 / ux1 behind a wait for the load, in the
+        // pass that issued it, and waits for the draw log's store of the pass before in front of every pass's row reads.)
+        if (t >= unext) {                                    // wavefront 0 alone
+            if (unext & (UWIN / 4)) {
                 ux0 = *(const SC_GLOBAL f4v*)(Uf + ulo + UWIN + 4 * lane);
                 ux1 = *(const SC_GLOBAL f4v*)(Uf + ulo + UWIN + 256 + 4 * lane);
-                upf = true;
             }
             if (t >= ulo + UWIN / 2) {
                 *(f4v*)(s_uwin + ((ulo & (UWIN - 1)) + 4 * lane)) = ux0;
                 *(f4v*)(s_uwin + ((ulo & (UWIN - 1)) + 256 + 4 * lane)) = ux1;
                 ulo += UWIN / 2;
-                upf = false;
             }
+            unext += UWIN / 4;
         }
         CHAIN_STAMP(3);
         issue_loads();                                       // rows of the new window first, then the commit
@@ -420,13 +439,14 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
         // the draw's strain goes to the region's draw log: a vector-memory byte store, which the barrier below (LDS counter
         // only) does not wait for.  The draws per (strain, read symbol) are counted from the log after the chain
         // (draw_log_counts): no pass reads them.
-        if (acc) *lg = (unsigned char)c;
+        if (acc) dlog[lg] = (unsigned char)c;
         CHAIN_STAMP_W(8);
+        if (t >= total) break;                               // (in front of the barrier: urn_chain_shadow leaves here too)
         lds_barrier();                                       // every wave's commits are in s_kf
         CHAIN_STAMP(4);
     }
 #ifdef SC_CHAIN_PROF
-    if (tid == 0) { for (int i = 0; i < 9; i++) if (i != 5) atomicAdd(&g_chain_prof[i], prof[i]); atomicAdd(&g_chain_prof[5], n_pass); }
+    if (tid == 0) { for (int i = 0; i < 9; i++) if (i != 5) atomicAdd(&g_chain_prof[i], (unsigned long long)prof[i]); atomicAdd(&g_chain_prof[5], (unsigned long long)n_pass); }
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the draw log's stores have left this wavefront ...
     __syncthreads();                                         // ... every wavefront's (draw_log_counts reads them)
