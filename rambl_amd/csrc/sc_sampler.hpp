@@ -213,6 +213,35 @@ template <int QP> __device__ __forceinline__ int quad_i32(int v) {
 }
 // LDS-only workgroup barrier: does not wait for outstanding global loads / stores
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// The same barrier, entered while the wavefront's N youngest LDS operations may still be in flight.  LDS operations of
+// one wavefront retire in the order they were issued, so once at most N are outstanding every LDS operation in front of
+// the N youngest has retired.  The caller has to know that at least N LDS operations follow, in the instruction stream,
+// the one the other wavefronts need; if more follow, the wait is merely stricter.  A scalar load shares the counter and
+// returns out of order with LDS: one outstanding here takes a place among the N and makes the wait stricter, never
+// weaker (the LDS operations outstanding are still the youngest, and there are still at most N of them).
+template <int N> __device__ __forceinline__ void lds_barrier_keep() {
+    static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
+    asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+// A scalar a loop reads, as the compiler sees it from here on: a value in scalar registers of unknown origin.  Whatever
+// loaded it has been waited for in front of this point, and the load can neither be repeated inside the loop nor be
+// moved to its head (profiles/level_latency, profiles/level_tail: a scalar load pending at the head of the pass loop
+// shares lgkmcnt with the loop's LDS reads and turns their staged waits into one wait for all).  64 bits go as two halves.
+// (readfirstlane: a resident workgroup reads its item out of LDS, so the compiler holds these uniform values in vector
+// registers there; on a value that is in scalar registers already it folds away.)
+template <class T> __device__ __forceinline__ T pin_scalar(T x) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two scalar registers");
+    if constexpr (sizeof(T) == 4) {
+        unsigned v = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, x));
+        asm volatile("" : "+s"(v));
+        return __builtin_bit_cast(T, v);
+    } else {
+        const unsigned long long w = __builtin_bit_cast(unsigned long long, x);
+        unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)w), hi = __builtin_amdgcn_readfirstlane((unsigned)(w >> 32));
+        asm volatile("" : "+s"(lo), "+s"(hi));
+        return __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
+    }
+}
 
 constexpr int UWIN = 1024;     // uniforms staged in LDS (fp32), refilled in halves
 #ifdef SC_CHAIN_PROF
@@ -223,6 +252,8 @@ constexpr int UWIN = 1024;     // uniforms staged in LDS (fp32), refilled in hal
 // front of them (CHAIN_STAMP_W): what is asynchronous in the product build -- the next rows' LDS reads, the atomic -- is
 // charged to its own part here, so the parts add up to more than the section costs when they overlap.  The last pass of a
 // level runs the commit section and its stamps like any other and leaves in front of the second barrier and its stamp.
+// (The product build issues the commit first and lets the bookkeeping and the reads run inside its latency: this build,
+// which waits at [7], cannot show that overlap.)
 __device__ unsigned long long g_chain_prof[12];
 #define CHAIN_STAMP(k) do { if (wv == 0) { const unsigned t_ = (unsigned)clock64(); prof[k] += t_ - tprev; tprev = t_; } } while (0)
 #define CHAIN_STAMP_W(k) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); CHAIN_STAMP(k); } while (0)
@@ -243,14 +274,17 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
     // (the wavefront's index as a scalar: what only wavefront 0 does -- the uniforms, the checked tiers -- then costs the
     // others a scalar branch instead of a walk through masked-off vector code)
     const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), k = lane & 3, pos = wv * 16 + (lane >> 2);
-    const int S = h.S, Q = h.Q, n = h.n_sweeps, e0 = h.e0;
+    // Every scalar the pass loop reads is pinned here (pin_scalar), the rare tiers' too: no scalar load is pending at the
+    // head of the loop or issued inside it, so lgkmcnt counts this wavefront's LDS operations alone there.
+    const int S = pin_scalar(h.S), Q = pin_scalar(h.Q), n = pin_scalar(h.n_sweeps), e0 = pin_scalar(h.e0);
+    stride = pin_scalar(stride);
     const int Sm1 = S - 1;
     const int total = n * Q;
-    const SlowArgs sa{job.qent, job.quid, job.ent_rid, job.ll, job.ll_stride, job.has};
-    const SC_GLOBAL double* Ustream = (const SC_GLOBAL double*)job.U;
-    const SC_GLOBAL float* Uf = (const SC_GLOBAL float*)job.Uf;
-    const SC_GLOBAL float* rows_g = (const SC_GLOBAL float*)job.tabLf;
-    SC_GLOBAL unsigned char* dlog = (SC_GLOBAL unsigned char*)job.dlog;
+    const SlowArgs sa{pin_scalar(job.qent), pin_scalar(job.quid), pin_scalar(job.ent_rid), pin_scalar(job.ll), pin_scalar(job.ll_stride), pin_scalar(job.has)};
+    const SC_GLOBAL double* Ustream = pin_scalar((const SC_GLOBAL double*)job.U);
+    const SC_GLOBAL float* Uf = pin_scalar((const SC_GLOBAL float*)job.Uf);
+    const SC_GLOBAL float* rows_g = pin_scalar((const SC_GLOBAL float*)job.tabLf);
+    SC_GLOBAL unsigned char* dlog = pin_scalar((SC_GLOBAL unsigned char*)job.dlog);
     auto ld4 = [&](int idx) __attribute__((always_inline)) -> f4v {
         return ROWS_LDS ? *(const f4v*)(rows_lds + idx) : *(const SC_GLOBAL f4v*)(rows_g + idx);
     };
@@ -401,6 +435,14 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
         const bool acc = (pos < adv) && (k == 0);
         const unsigned lg = (unsigned)(t + pos);                 // acc: t + pos < total <= JobDev::dlog_cap (the log: base + 32 bits)
         t += adv;
+        // The commit goes first: it is what the other wavefronts wait for at the second barrier, and everything else of
+        // this section -- the window's bookkeeping, the reads of the next window -- runs inside its latency, not in
+        // front of it.  Nothing below may be moved in front of it by the compiler (the reads would then be older than
+        // the atomic and the barrier's count would cover less than it says).  (profiles/chain_waits: worth 0.26 cycles
+        // per draw with the loop's scalars pinned, nothing without -- the two were measured apart.)
+        if (acc) __hip_atomic_fetch_add(&s_kf[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        asm volatile("" ::: "memory");
+        CHAIN_STAMP_W(7);
         // The row and the uniform of this lane's draw in the next window.  The last pass (t == total) moves them like any
         // other and loads what nobody uses, from inside the rows and the staged uniforms: ro stays below wrap (WIDE_Q:
         // ro < wrap and adv * stride <= 16 * NW * stride <= wrap, so r1 < 2 * wrap and the smaller of r1, r1 - wrap is
@@ -432,17 +474,27 @@ __device__ __forceinline__ void urn_chain_q(const JD& job, const LevelHdr& h, co
             unext += UWIN / 4;
         }
         CHAIN_STAMP(3);
-        issue_loads();                                       // rows of the new window first, then the commit
+        issue_loads();                                       // behind the commit: the youngest of them may cross the barrier below
         CHAIN_STAMP_W(6);
-        if (acc) __hip_atomic_fetch_add(&s_kf[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        CHAIN_STAMP_W(7);
         // the draw's strain goes to the region's draw log: a vector-memory byte store, which the barrier below (LDS counter
         // only) does not wait for.  The draws per (strain, read symbol) are counted from the log after the chain
         // (draw_log_counts): no pass reads them.
         if (acc) dlog[lg] = (unsigned char)c;
         CHAIN_STAMP_W(8);
         if (t >= total) break;                               // (in front of the barrier: urn_chain_shadow leaves here too)
-        lds_barrier();                                       // every wave's commits are in s_kf
+        // Every wavefront's commits are in s_kf behind this barrier, which waits for the commit and not for the reads
+        // issued behind it (lds_barrier_keep).  Behind the atomic this wavefront has issued, in this order: the refill's
+        // two LDS writes (wavefront 0, some passes), then issue_loads() -- with the rows in LDS the NQ 16-byte reads of
+        // L[g], which the compiler can neither merge nor leave out, and the reads of llast and uf; with the rows in memory
+        // the read of uf alone, the rows being global loads that no LDS barrier ever waited for.  So at least NQ (or
+        // one) LDS operations are younger than the atomic, and once at most that many are outstanding the atomic has
+        // retired; llast and uf, counted or not, only make the wait stricter, and so do the refill's writes.  Those
+        // need not be waited for here at all: they fill the half of s_uwin that no draw reads before the window has
+        // moved on by a quarter of UWIN, several passes on, and wavefront 0 passes the next pass's first barrier --
+        // lgkmcnt(0) -- before anyone gets there.  The reads left in flight are this wavefront's own; the compiler waits
+        // for them where the next pass uses them.  The pass that leaves the loop leaves in front of this barrier, and the
+        // closing __syncthreads() drains whatever it left.
+        lds_barrier_keep<ROWS_LDS ? NQ : 1>();
         CHAIN_STAMP(4);
     }
 #ifdef SC_CHAIN_PROF
