@@ -210,6 +210,25 @@ int sc_update_level(sc_ctx* ctx, int S, const int* slot, const int* lab_off, con
                     const unsigned char* ent_first, int n_copy, const int* copy_src, const int* copy_dst, int copy_n,
                     double* ll_out, unsigned char* has_out, unsigned char* isnew_out, int* done_out);
 
+/* Row a15 on its own, for tests: the hard update of one level (hard_clustering, NonparametricClustering.cpp:17-125) behind
+ * the level's update, as every level in front of the first branching runs it: the level of sc_update_level with mode hard,
+ * through the production level kernel and, where the level goes there, the grid kernels in front of it.  Everything
+ * sc_update_level takes, with its checks, and: logpri[S] the strains' log priors (-inf is log 0; NaN and +inf are refused),
+ * ent_cn[n_ent] >= 1 the entries' copy numbers, the mates as a CSR over the reads (mate_off[n_reads+1], mate_idx in
+ * [-1, n_reads), -1: none).  Entry r yields ent_cn[r] draw slots, Q of them in all (1 .. 2^20).  In a level with any label of
+ * more than one symbol every code of every entry's label is below K (the hard update walks each against every strain's);
+ * a strain's single symbol may hold any code ("^" and "$" carry 0xFF), it then counts nowhere.  Out, beside what
+ * sc_update_level returns (now behind the hard update: a mate not seen before has a zero in the rows of the level's
+ * strains and is present): abund[S], subst[S*K*K], the responsibilities resp[s*Q + q], and the draw slots as the device
+ * wrote them, qrid[Q], quid[Q], qcode[Q]. */
+int sc_hard_level(sc_ctx* ctx, int S, const int* slot, const int* lab_off, const int* lab_len, int K, int code_N,
+                  const double* lpt, const double* logpri, int n_reads, const double* ll, const unsigned char* has,
+                  const unsigned char* labels, int n_labels, int n_ent, int e0, const int* ent_rid, const int* ent_cn,
+                  const int* ent_lab_off, const int* ent_lab_len, const unsigned char* ent_first, const int* mate_off,
+                  const int* mate_idx, int n_copy, const int* copy_src, const int* copy_dst, int copy_n, double* ll_out,
+                  unsigned char* has_out, unsigned char* isnew_out, double* abund, double* subst, double* resp, int* qrid,
+                  int* quid, unsigned char* qcode, int* done_out);
+
 /* ---- rows a2-a4 on the host: the alignment file and a window's reads (rambl_amd/csrc/sc_aln_file.cpp, sc_ingest.cpp) ----------
  *
  * The reference shells out to samtools for every window (StrainCall.cpp:496 `view -q mq -F 1804 region`, :696

@@ -109,6 +109,8 @@ ENTRIES = [
     ("sc_sample_level", _i, [_vp, _i, _dp, _i, _dp, _bp, _i, _i, _ip, _ip, _ip, _ip, _ip, _i, _dp, _i, _up, _up, _lp]),
     ("sc_update_level", _i, [_vp, _i, _ip, _ip, _ip, _i, _i, _dp, _i, _dp, _bp, _bp, _i, _i, _i, _ip, _ip, _ip, _bp, _i, _ip, _ip, _i,
                              _dp, _bp, _bp, _ip]),
+    ("sc_hard_level", _i, [_vp, _i, _ip, _ip, _ip, _i, _i, _dp, _dp, _i, _dp, _bp, _bp, _i, _i, _i, _ip, _ip, _ip, _ip, _bp, _ip, _ip, _i,
+                           _ip, _ip, _i, _dp, _bp, _bp, _dp, _dp, _dp, _ip, _ip, _bp, _ip]),
     ("sc_aln_open", _i, [_s, _vpp]),
     ("sc_aln_open_filtered", _i, [_s, _sp, _i, _vpp]),
     ("sc_aln_close", None, [_vp]),
@@ -385,6 +387,35 @@ class RegionResult:
         self.stats = stats
 
 
+class _LevelArrays:
+    """What Context.update_level and Context.hard_level both pass: one level's strains, labels, rows and entries as the
+    arrays the library takes, and the buffers of what both return."""
+
+    def __init__(self, slot, strain_labels, K, lpt, ll, has, ent_rid, ent_labels, ent_first, copies):
+        import numpy as np
+        self.ll = np.ascontiguousarray(ll, dtype=np.float64)
+        self.S, self.n_reads = S, n_reads = self.ll.shape
+        self.lpt = np.ascontiguousarray(lpt, dtype=np.float64)
+        assert self.lpt.shape == (S, K, K) and len(slot) == len(strain_labels) == S
+        self.has = np.ascontiguousarray(has, dtype=np.uint8)
+        assert self.has.shape == (n_reads,) and len(ent_rid) == len(ent_labels) == len(ent_first)
+        labels = [list(x) for x in list(strain_labels) + list(ent_labels)]
+        lab_len = np.array([len(x) for x in labels], dtype=np.int32)
+        lab_off = np.ascontiguousarray(np.concatenate(([0], np.cumsum(lab_len)[:-1])), dtype=np.int32)
+        self.codes = np.array([c for x in labels for c in x] or [0], dtype=np.uint8)
+        self.slot, self.rid = (np.ascontiguousarray(x, dtype=np.int32) for x in (slot, ent_rid))
+        self.first = np.ascontiguousarray(ent_first, dtype=np.uint8)
+        self.src, self.dst = (np.array([p[k] for p in copies] or [0], dtype=np.int32) for k in (0, 1))
+        self.s_off, self.s_len, self.e_off, self.e_len = (np.ascontiguousarray(x) for x in (lab_off[:S], lab_len[:S], lab_off[S:], lab_len[S:]))
+        self.ll_out = np.zeros((128, n_reads), dtype=np.float64)
+        self.has_out = np.zeros(n_reads, dtype=np.uint8)
+        self.isnew = np.zeros(max(len(self.rid), 1), dtype=np.uint8)
+        self.done = C.c_int()
+
+    def result(self):
+        return dict(ll=self.ll_out, has=self.has_out, isnew=self.isnew[:len(self.rid)], done=self.done.value)
+
+
 class Context:
     """One HIP device, `streams` regions in flight."""
 
@@ -562,31 +593,40 @@ class Context:
         sequence of symbol codes, lpt: [S][K][K], ll: [S][n_reads] the strains' rows before the level, has: [n_reads],
         ent_first: [n_ent] (0: the read occurred earlier in the level), copies: (source row, destination row) pairs.
         Returns dict(ll[128][n_reads]: the whole matrix, has, isnew[n_ent], done: the pieces that ran on a grid)."""
-        import numpy as np
-        ll = np.ascontiguousarray(ll, dtype=np.float64)
-        S, n_reads = ll.shape
-        lpt = np.ascontiguousarray(lpt, dtype=np.float64)
-        assert lpt.shape == (S, K, K) and len(slot) == len(strain_labels) == S
-        has = np.ascontiguousarray(has, dtype=np.uint8)
-        assert has.shape == (n_reads,) and len(ent_rid) == len(ent_labels) == len(ent_first)
-        labels = [list(x) for x in list(strain_labels) + list(ent_labels)]
-        lab_len = np.array([len(x) for x in labels], dtype=np.int32)
-        lab_off = np.ascontiguousarray(np.concatenate(([0], np.cumsum(lab_len)[:-1])), dtype=np.int32)
-        codes = np.array([c for x in labels for c in x] or [0], dtype=np.uint8)
-        slot, rid = (np.ascontiguousarray(x, dtype=np.int32) for x in (slot, ent_rid))
-        first = np.ascontiguousarray(ent_first, dtype=np.uint8)
-        src, dst = (np.array([p[k] for p in copies] or [0], dtype=np.int32) for k in (0, 1))
-        s_off, s_len, e_off, e_len = (np.ascontiguousarray(x) for x in (lab_off[:S], lab_len[:S], lab_off[S:], lab_len[S:]))
-        ll_out = np.zeros((128, n_reads), dtype=np.float64)
-        has_out = np.zeros(n_reads, dtype=np.uint8)
-        isnew = np.zeros(max(len(rid), 1), dtype=np.uint8)
-        done = C.c_int()
-        rc = self.lib.sc_update_level(self.h, S, _ptr(slot), _ptr(s_off), _ptr(s_len), K, code_N, _ptr(lpt), n_reads, _ptr(ll), _ptr(has),
-                                      _ptr(codes), len(codes), len(rid), e0, _ptr(rid), _ptr(e_off), _ptr(e_len), _ptr(first),
-                                      len(copies), _ptr(src), _ptr(dst), copy_n, _ptr(ll_out), _ptr(has_out), _ptr(isnew), C.byref(done))
+        a = _LevelArrays(slot, strain_labels, K, lpt, ll, has, ent_rid, ent_labels, ent_first, copies)
+        rc = self.lib.sc_update_level(self.h, a.S, _ptr(a.slot), _ptr(a.s_off), _ptr(a.s_len), K, code_N, _ptr(a.lpt), a.n_reads, _ptr(a.ll),
+                                      _ptr(a.has), _ptr(a.codes), len(a.codes), len(a.rid), e0, _ptr(a.rid), _ptr(a.e_off), _ptr(a.e_len),
+                                      _ptr(a.first), len(copies), _ptr(a.src), _ptr(a.dst), copy_n, _ptr(a.ll_out), _ptr(a.has_out),
+                                      _ptr(a.isnew), C.byref(a.done))
         if rc != SC_OK:
             raise self._err(rc)
-        return dict(ll=ll_out, has=has_out, isnew=isnew[:len(rid)], done=done.value)
+        return a.result()
+
+    def hard_level(self, slot, strain_labels, K, code_N, lpt, ll, has, ent_rid, ent_labels, ent_first, logpri, ent_cn, mates, copies=(),
+                   copy_n=0, e0=1):
+        """Row a15 on its own (a test entry): the level of update_level with the hard update behind its update.  logpri: [S] the
+        strains' log priors, ent_cn: [n_ent] copy numbers, mates: per read a list of mate ids (-1: none), as sample_level.
+        Returns what update_level returns (behind the hard update) and abund[S], subst[S][K][K], resp[S][Q], qrid[Q], quid[Q],
+        qcode[Q]."""
+        import numpy as np
+        a = _LevelArrays(slot, strain_labels, K, lpt, ll, has, ent_rid, ent_labels, ent_first, copies)
+        logpri = np.ascontiguousarray(logpri, dtype=np.float64)
+        cn = np.ascontiguousarray(ent_cn, dtype=np.int32)
+        assert logpri.shape == (a.S,) and cn.shape == a.rid.shape
+        mate_off = np.zeros(a.n_reads + 1, dtype=np.int32)
+        mate_off[1:] = np.cumsum([len(mates[r]) if r < len(mates) else 0 for r in range(a.n_reads)])
+        mate_idx = np.array([m for r in range(min(len(mates), a.n_reads)) for m in mates[r]] or [0], dtype=np.int32)
+        Q = max(int(cn.sum()), 1)
+        abund, subst, resp = np.zeros(a.S), np.zeros((a.S, K, K)), np.zeros((a.S, Q))
+        qrid, quid, qcode = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.uint8)
+        rc = self.lib.sc_hard_level(self.h, a.S, _ptr(a.slot), _ptr(a.s_off), _ptr(a.s_len), K, code_N, _ptr(a.lpt), _ptr(logpri), a.n_reads,
+                                    _ptr(a.ll), _ptr(a.has), _ptr(a.codes), len(a.codes), len(a.rid), e0, _ptr(a.rid), _ptr(cn), _ptr(a.e_off),
+                                    _ptr(a.e_len), _ptr(a.first), _ptr(mate_off), _ptr(mate_idx), len(copies), _ptr(a.src), _ptr(a.dst), copy_n,
+                                    _ptr(a.ll_out), _ptr(a.has_out), _ptr(a.isnew), _ptr(abund), _ptr(subst), _ptr(resp), _ptr(qrid),
+                                    _ptr(quid), _ptr(qcode), C.byref(a.done))
+        if rc != SC_OK:
+            raise self._err(rc)
+        return dict(a.result(), abund=abund, subst=subst, resp=resp, qrid=qrid, quid=quid, qcode=qcode)
 
     def msa_align(self, seqs):
         """Row a7: rows of the progressive sum-of-pairs MSA of `seqs` (in the given order)."""

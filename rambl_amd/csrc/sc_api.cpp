@@ -9,7 +9,7 @@
 #include "sc_ctx.hpp"
 
 using namespace sc;
-// What the one-level test entries (sc_sample_level, sc_update_level) share: a region that is nothing but one level.  Its
+// What the one-level test entries (sc_sample_level, sc_update_level, sc_hard_level) share: a region that is nothing but one level.  Its
 // entries lie at [e0, e0 + n_ent) of the region's arrays; entries [0, e0) belong to other levels: they name other reads (the
 // last ones, backwards), so that an entry index that misses e0 reads the wrong row.  The vectors live as long as the stub:
 // the copies of a private worker pass through, so their sources stay until the stream is synchronised.
@@ -60,6 +60,160 @@ template <class F> static int ctx_guarded(Ctx* ctx, const char* fn, F&& body) no
     const int rc = guarded(&err, fn, body);
     if (!err.text.empty()) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->last_error.swap(err.text); }
     return rc;
+}
+
+// One level on hand-made inputs, as sc_update_level and sc_hard_level state it (include/straincall_hip.h): the arguments
+// both take ...
+struct OneLevel {
+    int S; const int *slot, *lab_off, *lab_len; int K, code_N; const double* lpt;
+    int n_reads; const double* ll; const unsigned char *has, *labels; int n_labels, n_ent, e0;
+    const int *ent_rid, *ent_lab_off, *ent_lab_len; const unsigned char* ent_first;
+    int n_copy; const int *copy_src, *copy_dst; int copy_n;
+    double* ll_out; unsigned char *has_out, *isnew_out; int* done_out;
+};
+// ... and what the hard update adds: the strains' log priors, the entries' copy numbers, the mates (CSR over the reads), and
+// its results.
+struct HardLevel {
+    const double* logpri; const int *ent_cn, *mate_off, *mate_idx;
+    double *abund, *subst, *resp; int *qrid, *quid; unsigned char* qcode;
+};
+// The checks, the stub region, the level's parameters, the launch through launch_level and the copies back, for both
+// entries.  hard = nullptr: the update alone (the level's kernel returns behind it); else MODE_HARD behind the update, as
+// LevelWalk::hard_clustering runs it.
+static int one_level(sc_ctx* h, const char* fn, const OneLevel& a, const HardLevel* hard) {
+    if (!h || !a.slot || !a.lab_off || !a.lab_len || !a.lpt || !a.ll || !a.has || !a.labels || !a.ent_rid || !a.ent_lab_off || !a.ent_lab_len ||
+        !a.ent_first || !a.ll_out || !a.has_out || !a.isnew_out || !a.done_out)
+        return SC_ERR_ARG;
+    if (hard && (!hard->logpri || !hard->ent_cn || !hard->mate_off || !hard->abund || !hard->subst || !hard->resp || !hard->qrid || !hard->quid ||
+                 !hard->qcode))
+        return SC_ERR_ARG;
+    Ctx* ctx = &h->c;
+    if (ctx->resident || ctx->workers.size() != 1) return SC_ERR_ARG;      // as sc_sample_level
+    const int S = a.S, K = a.K, code_N = a.code_N, n_reads = a.n_reads, n_ent = a.n_ent, e0 = a.e0, n_labels = a.n_labels, n_copy = a.n_copy;
+    if (S < 1 || S > MAXS || K < 6 || K > KMAX || !(code_N == -1 || (code_N >= 6 && code_N < K)) || n_reads < 1 ||
+        n_reads > (1 << 16) || n_ent < 1 || n_ent > (1 << 16) || e0 < 0 || e0 > (1 << 20) || n_labels < 1 || n_labels > (1 << 24) || n_copy < 0 || n_copy > MAXS || a.copy_n < 0)
+        return SC_ERR_ARG;
+    if ((long)S * K * K > (long)level_table_capacity()) return SC_ERR_ARG;
+    if (n_copy > 0 && (!a.copy_src || !a.copy_dst)) return SC_ERR_ARG;
+    // Everything a kernel indexes with.  A label lies inside `labels`.  The update: a label of a single symbol may hold any
+    // code (its single-symbol paths check a < K && b < K themselves); the walks over a multi-symbol label index the strain's
+    // table unchecked, so every code they meet is below K (an N of the strain's label becomes the read's symbol first): the
+    // codes of every multi-symbol label, and of every entry's label once a strain's label has more than one symbol.  The hard
+    // update of a level with any multi-symbol label walks every entry's label against every strain's: there every entry's
+    // codes are below K, whatever the strains' labels are.  (A strain's single symbol stays free: "^" and "$" carry 0xFF in
+    // production, and both updates test it.)
+    auto label_ok = [&](int off, int len, bool strain, bool walked) {
+        if (len < 1 || off < 0 || (long)off + len > (long)n_labels) return false;
+        if (len == 1 && !walked) return true;
+        for (int i = 0; i < len; i++) {
+            const int c = a.labels[off + i];
+            if (!(c < K || (strain && c == code_N))) return false;
+        }
+        return true;
+    };
+    bool multi_strain = false;
+    uint64_t taken[2] = {0, 0}, dst_rows[2] = {0, 0}, src_rows[2] = {0, 0};
+    auto bit = [](const uint64_t* m, int r) { return (m[r >> 6] >> (r & 63)) & 1; };
+    auto set = [](uint64_t* m, int r) { m[r >> 6] |= 1ull << (r & 63); };
+    for (int s = 0; s < S; s++) {
+        if (a.slot[s] < 0 || a.slot[s] >= MAXS || bit(taken, a.slot[s])) return SC_ERR_ARG;
+        set(taken, a.slot[s]);
+        if (!label_ok(a.lab_off[s], a.lab_len[s], true, a.lab_len[s] > 1)) return SC_ERR_ARG;
+        if (a.lab_len[s] > 1) multi_strain = true;
+        if (hard && !(hard->logpri[s] < INFINITY)) return SC_ERR_ARG;      // (-inf is log 0; NaN and +inf are no log of a share)
+    }
+    bool has_dups = false, any_multi = multi_strain;
+    for (int r = 0; r < n_ent; r++) {
+        if (!a.ent_first[r]) has_dups = true;                 // as LevelWalk::run derives them from the level's entries
+        if (a.ent_lab_len[r] != 1) any_multi = true;
+    }
+    long Q = 0;
+    for (int r = 0; r < n_ent; r++) {
+        if (a.ent_rid[r] < 0 || a.ent_rid[r] >= n_reads || !label_ok(a.ent_lab_off[r], a.ent_lab_len[r], false, hard ? any_multi : multi_strain)) return SC_ERR_ARG;
+        if (hard && hard->ent_cn[r] < 1) return SC_ERR_ARG;
+        Q += hard ? hard->ent_cn[r] : 1;
+    }
+    if (Q < 1 || Q > (1L << 20)) return SC_ERR_ARG;          // (tabA holds MAXS * Q doubles)
+    int nm = 0;
+    if (hard) {
+        if (hard->mate_off[0] != 0) return SC_ERR_ARG;
+        for (int r = 0; r < n_reads; r++) if (hard->mate_off[r + 1] < hard->mate_off[r]) return SC_ERR_ARG;
+        nm = hard->mate_off[n_reads];
+        if (nm > 0 && !hard->mate_idx) return SC_ERR_ARG;
+        for (int i = 0; i < nm; i++) if (hard->mate_idx[i] < -1 || hard->mate_idx[i] >= n_reads) return SC_ERR_ARG;
+    }
+    // the copies are independent: a destination is no other pair's destination and nobody's source
+    for (int c = 0; c < n_copy; c++) {
+        if (a.copy_src[c] < 0 || a.copy_src[c] >= MAXS || a.copy_dst[c] < 0 || a.copy_dst[c] >= MAXS || bit(dst_rows, a.copy_dst[c])) return SC_ERR_ARG;
+        set(dst_rows, a.copy_dst[c]); set(src_rows, a.copy_src[c]);
+    }
+    if ((dst_rows[0] & src_rows[0]) || (dst_rows[1] & src_rows[1])) return SC_ERR_ARG;
+    return ctx_guarded(ctx, fn, [&] {
+        Worker w;                                      // a private worker: own stream, own parameter / result blocks
+        w.init_private(ctx);
+        const int E = e0 + n_ent;
+        LevelStub stub;
+        FlatGraph& f = stub.f;
+        f.K = K; f.code_N = code_N;
+        stub.entries(e0, n_ent, n_reads, (size_t)e0 + (size_t)n_labels);      // the caller's labels behind those of the entries in front
+        std::memcpy(f.labels.data() + e0, a.labels, (size_t)n_labels);
+        for (int r = 0, q = 0; r < n_ent; r++) {
+            const size_t e = (size_t)(e0 + r);
+            f.ent_rid[e] = a.ent_rid[r]; f.ent_lab_off[e] = e0 + a.ent_lab_off[r]; f.ent_lab_len[e] = a.ent_lab_len[r];
+            f.ent_first[e] = a.ent_first[r] ? 1 : 0;
+            f.ent_cn[e] = hard ? hard->ent_cn[r] : 1;
+            stub.qoff[e] = q; q += f.ent_cn[e];
+        }
+        if (hard) {
+            stub.mptr.assign(hard->mate_off, hard->mate_off + n_reads + 1);
+            if (nm > 0) stub.midx.assign(hard->mate_idx, hard->mate_idx + nm);
+        }
+        const hipStream_t st = w.st;
+        const JobDev& jd = stub.upload(w, n_reads, Q, n_ent, 1, S, a.slot, a.ll, a.has);
+        const JobDev* jd_dev = stub.publish(w);
+
+        // the level's parameters as LevelWalk::run_level states them
+        LevelParams& P = *w.Ph;
+        for (int s = 0; s < S; s++) {
+            P.sp[s] = StrainParam{a.slot[s], e0 + a.lab_off[s], a.lab_len[s], 0, 1.0, hard ? hard->logpri[s] : 0.0};
+            w.hp.logpri[s] = P.sp[s].logpri;
+            w.gp.slot[s] = (uint8_t)a.slot[s];
+            w.gp.lab[s] = f.labels[(size_t)(e0 + a.lab_off[s])];
+        }
+        for (int c = 0; c < n_copy; c++) {
+            P.copy_src[c] = a.copy_src[c]; P.copy_dst[c] = a.copy_dst[c];
+            w.gp.copy_src[c] = (uint8_t)a.copy_src[c]; w.gp.copy_dst[c] = (uint8_t)a.copy_dst[c];
+        }
+        std::memcpy(P.lpt, a.lpt, sizeof(double) * (size_t)S * K * K);             // compact [K][K]
+        LevelHdr H{};
+        H.mode = hard ? MODE_HARD : MODE_SAMPLE; H.S = S; H.e0 = e0; H.e1 = E; H.has_dups = has_dups; H.any_multi = any_multi; H.Q = (int)Q;
+        H.n_sweeps = 0;                                // no sampler: level_kind gives 0, level_plain_body returns behind the update or runs the hard update
+        H.n_copy = n_copy; H.copy_n = a.copy_n; H.do_update = 1; H.seq = 1;
+        std::memset(w.Rh, 0, sizeof(LevelResult));
+        const LevelItem it = w.level_item(jd_dev, H, K);
+        if (item_kind(it.kind) != 0) throw ScError(SC_ERR_INTERNAL, "a level without sweeps asked for the sampler");
+        const int done = launch_level(st, it, w.gp, w.hp, n_reads);      // as the walk of a single region launches its levels
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        if (w.Rh->seq != 1u || w.Rh->error) throw ScError(SC_ERR_INTERNAL, "the level did not complete");
+        std::vector<double>& rows = stub.rows;         // the whole matrix back, without the padding of its stride
+        HIPCHK(hipMemcpy(rows.data(), jd.ll, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+        for (int r = 0; r < MAXS; r++) std::memcpy(a.ll_out + (size_t)r * n_reads, &rows[(size_t)r * jd.ll_stride], sizeof(double) * (size_t)n_reads);
+        HIPCHK(hipMemcpy(a.has_out, jd.has, (size_t)n_reads, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(a.isnew_out, jd.isnew, (size_t)n_ent, hipMemcpyDeviceToHost));
+        if (hard) {
+            std::memcpy(hard->abund, w.Rh->abund, sizeof(double) * (size_t)S);
+            std::memcpy(hard->subst, w.Rh->subst, sizeof(double) * (size_t)S * K * K);
+            // the responsibilities tabA[s * qcap + q], without their stride; the draw slots as the device wrote them
+            for (int s = 0; s < S; s++)
+                HIPCHK(hipMemcpy(hard->resp + (size_t)s * Q, jd.tabA + (size_t)s * jd.qcap, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hard->qrid, jd.qrid, sizeof(int) * (size_t)Q, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hard->quid, jd.quid, sizeof(int) * (size_t)Q, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hard->qcode, jd.qcode, (size_t)Q, hipMemcpyDeviceToHost));
+        }
+        *a.done_out = done;
+        return SC_OK;
+    });
 }
 
 extern "C" {
@@ -399,101 +553,27 @@ int sc_update_level(sc_ctx* h, int S, const int* slot, const int* lab_off, const
                     int e0, const int* ent_rid, const int* ent_lab_off, const int* ent_lab_len, const unsigned char* ent_first,
                     int n_copy, const int* copy_src, const int* copy_dst, int copy_n, double* ll_out, unsigned char* has_out,
                     unsigned char* isnew_out, int* done_out) {
-    if (!h || !slot || !lab_off || !lab_len || !lpt || !ll || !has || !labels || !ent_rid || !ent_lab_off || !ent_lab_len || !ent_first ||
-        !ll_out || !has_out || !isnew_out || !done_out)
-        return SC_ERR_ARG;
-    Ctx* ctx = &h->c;
-    if (ctx->resident || ctx->workers.size() != 1) return SC_ERR_ARG;      // as sc_sample_level
-    if (S < 1 || S > MAXS || K < 6 || K > KMAX || !(code_N == -1 || (code_N >= 6 && code_N < K)) || n_reads < 1 ||
-        n_reads > (1 << 16) || n_ent < 1 || n_ent > (1 << 16) || e0 < 0 || e0 > (1 << 20) || n_labels < 1 || n_labels > (1 << 24) || n_copy < 0 || n_copy > MAXS || copy_n < 0)
-        return SC_ERR_ARG;
-    if ((long)S * K * K > (long)level_table_capacity()) return SC_ERR_ARG;
-    if (n_copy > 0 && (!copy_src || !copy_dst)) return SC_ERR_ARG;
-    // Everything a kernel indexes with.  A label lies inside `labels`; one of a single symbol may hold any code (the
-    // single-symbol paths check a < K && b < K themselves); the walks over a multi-symbol label index the strain's table
-    // unchecked, so every code they meet is below K (an N of the strain's label becomes the read's symbol first): the codes
-    // of every multi-symbol label, and of every entry's label once a strain's label has more than one symbol.
-    auto label_ok = [&](int off, int len, bool strain, bool walked) {
-        if (len < 1 || off < 0 || (long)off + len > (long)n_labels) return false;
-        if (len == 1 && !walked) return true;
-        for (int i = 0; i < len; i++) {
-            const int c = labels[off + i];
-            if (!(c < K || (strain && c == code_N))) return false;
-        }
-        return true;
-    };
-    bool multi_strain = false;
-    uint64_t taken[2] = {0, 0}, dst_rows[2] = {0, 0}, src_rows[2] = {0, 0};
-    auto bit = [](const uint64_t* m, int r) { return (m[r >> 6] >> (r & 63)) & 1; };
-    auto set = [](uint64_t* m, int r) { m[r >> 6] |= 1ull << (r & 63); };
-    for (int s = 0; s < S; s++) {
-        if (slot[s] < 0 || slot[s] >= MAXS || bit(taken, slot[s])) return SC_ERR_ARG;
-        set(taken, slot[s]);
-        if (!label_ok(lab_off[s], lab_len[s], true, lab_len[s] > 1)) return SC_ERR_ARG;
-        if (lab_len[s] > 1) multi_strain = true;
-    }
-    bool has_dups = false, any_multi = multi_strain;
-    for (int r = 0; r < n_ent; r++) {
-        if (ent_rid[r] < 0 || ent_rid[r] >= n_reads || !label_ok(ent_lab_off[r], ent_lab_len[r], false, multi_strain)) return SC_ERR_ARG;
-        if (!ent_first[r]) has_dups = true;                 // as LevelWalk::run derives them from the level's entries
-        if (ent_lab_len[r] != 1) any_multi = true;
-    }
-    // the copies are independent: a destination is no other pair's destination and nobody's source
-    for (int c = 0; c < n_copy; c++) {
-        if (copy_src[c] < 0 || copy_src[c] >= MAXS || copy_dst[c] < 0 || copy_dst[c] >= MAXS || bit(dst_rows, copy_dst[c])) return SC_ERR_ARG;
-        set(dst_rows, copy_dst[c]); set(src_rows, copy_src[c]);
-    }
-    if ((dst_rows[0] & src_rows[0]) || (dst_rows[1] & src_rows[1])) return SC_ERR_ARG;
-    return ctx_guarded(ctx, "sc_update_level", [&] {
-        Worker w;                                      // a private worker: own stream, own parameter / result blocks
-        w.init_private(ctx);
-        const int E = e0 + n_ent;
-        LevelStub stub;
-        FlatGraph& f = stub.f;
-        f.K = K; f.code_N = code_N;
-        stub.entries(e0, n_ent, n_reads, (size_t)e0 + (size_t)n_labels);      // the caller's labels behind those of the entries in front
-        std::memcpy(f.labels.data() + e0, labels, (size_t)n_labels);
-        for (int r = 0; r < n_ent; r++) {
-            const size_t e = (size_t)(e0 + r);
-            f.ent_rid[e] = ent_rid[r]; f.ent_lab_off[e] = e0 + ent_lab_off[r]; f.ent_lab_len[e] = ent_lab_len[r];
-            f.ent_first[e] = ent_first[r] ? 1 : 0;
-            stub.qoff[e] = r;
-        }
-        const hipStream_t st = w.st;
-        const JobDev& jd = stub.upload(w, n_reads, n_ent, n_ent, 1, S, slot, ll, has);
-        const JobDev* jd_dev = stub.publish(w);
-
-        // the level's parameters as LevelWalk::run_level states them
-        LevelParams& P = *w.Ph;
-        for (int s = 0; s < S; s++) {
-            P.sp[s] = StrainParam{slot[s], e0 + lab_off[s], lab_len[s], 0, 1.0, 0.0};
-            w.gp.slot[s] = (uint8_t)slot[s];
-            w.gp.lab[s] = f.labels[(size_t)(e0 + lab_off[s])];
-        }
-        for (int c = 0; c < n_copy; c++) {
-            P.copy_src[c] = copy_src[c]; P.copy_dst[c] = copy_dst[c];
-            w.gp.copy_src[c] = (uint8_t)copy_src[c]; w.gp.copy_dst[c] = (uint8_t)copy_dst[c];
-        }
-        std::memcpy(P.lpt, lpt, sizeof(double) * (size_t)S * K * K);             // compact [K][K]
-        LevelHdr H{};
-        H.mode = MODE_SAMPLE; H.S = S; H.e0 = e0; H.e1 = E; H.has_dups = has_dups; H.any_multi = any_multi; H.Q = n_ent;
-        H.n_sweeps = 0;                                // no sampler: level_kind gives 0, level_plain_body returns behind the update
-        H.n_copy = n_copy; H.copy_n = copy_n; H.do_update = 1; H.seq = 1;
-        std::memset(w.Rh, 0, sizeof(LevelResult));
-        const LevelItem it = w.level_item(jd_dev, H, K);
-        if (item_kind(it.kind) != 0) throw ScError(SC_ERR_INTERNAL, "a level without sweeps asked for the sampler");
-        const int done = launch_level(st, it, w.gp, w.hp, n_reads);      // as the walk of a single region launches its levels
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-        if (w.Rh->seq != 1u || w.Rh->error) throw ScError(SC_ERR_INTERNAL, "the level did not complete");
-        std::vector<double>& rows = stub.rows;         // the whole matrix back, without the padding of its stride
-        HIPCHK(hipMemcpy(rows.data(), jd.ll, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
-        for (int r = 0; r < MAXS; r++) std::memcpy(ll_out + (size_t)r * n_reads, &rows[(size_t)r * jd.ll_stride], sizeof(double) * (size_t)n_reads);
-        HIPCHK(hipMemcpy(has_out, jd.has, (size_t)n_reads, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(isnew_out, jd.isnew, (size_t)n_ent, hipMemcpyDeviceToHost));
-        *done_out = done;
-        return SC_OK;
-    });
+    OneLevel a{};
+    a.S = S; a.slot = slot; a.lab_off = lab_off; a.lab_len = lab_len; a.K = K; a.code_N = code_N; a.lpt = lpt; a.n_reads = n_reads;
+    a.ll = ll; a.has = has; a.labels = labels; a.n_labels = n_labels; a.n_ent = n_ent; a.e0 = e0; a.ent_rid = ent_rid;
+    a.ent_lab_off = ent_lab_off; a.ent_lab_len = ent_lab_len; a.ent_first = ent_first; a.n_copy = n_copy; a.copy_src = copy_src;
+    a.copy_dst = copy_dst; a.copy_n = copy_n; a.ll_out = ll_out; a.has_out = has_out; a.isnew_out = isnew_out; a.done_out = done_out;
+    return one_level(h, "sc_update_level", a, nullptr);
+}
+int sc_hard_level(sc_ctx* h, int S, const int* slot, const int* lab_off, const int* lab_len, int K, int code_N, const double* lpt,
+                  const double* logpri, int n_reads, const double* ll, const unsigned char* has, const unsigned char* labels,
+                  int n_labels, int n_ent, int e0, const int* ent_rid, const int* ent_cn, const int* ent_lab_off,
+                  const int* ent_lab_len, const unsigned char* ent_first, const int* mate_off, const int* mate_idx, int n_copy,
+                  const int* copy_src, const int* copy_dst, int copy_n, double* ll_out, unsigned char* has_out,
+                  unsigned char* isnew_out, double* abund, double* subst, double* resp, int* qrid, int* quid, unsigned char* qcode,
+                  int* done_out) {
+    OneLevel a{};
+    a.S = S; a.slot = slot; a.lab_off = lab_off; a.lab_len = lab_len; a.K = K; a.code_N = code_N; a.lpt = lpt; a.n_reads = n_reads;
+    a.ll = ll; a.has = has; a.labels = labels; a.n_labels = n_labels; a.n_ent = n_ent; a.e0 = e0; a.ent_rid = ent_rid;
+    a.ent_lab_off = ent_lab_off; a.ent_lab_len = ent_lab_len; a.ent_first = ent_first; a.n_copy = n_copy; a.copy_src = copy_src;
+    a.copy_dst = copy_dst; a.copy_n = copy_n; a.ll_out = ll_out; a.has_out = has_out; a.isnew_out = isnew_out; a.done_out = done_out;
+    const HardLevel hd{logpri, ent_cn, mate_off, mate_idx, abund, subst, resp, qrid, quid, qcode};
+    return one_level(h, "sc_hard_level", a, &hd);
 }
 int sc_roi_release(sc_ctx* h, int handle) {
     if (!h) return SC_ERR_ARG;

@@ -568,6 +568,9 @@ __device__ __forceinline__ void level_plain_body(const IT& it, unsigned char* s_
             const uint8_t* sb = job.labels + l.s_sp[s].lab_off;
             const int ls = l.s_sp[s].lab_len;
             double acc = 0;
+            // a strain on "^" or "$" carries the code 0xFF, which is no row of the histogram (the one-wavefront path and
+            // k_hard_sums drop it the same way; the host reads the rows below K alone)
+            auto add = [&](int a, int b, double p) __attribute__((always_inline)) { if (a < K && b < K) hist[a * K + b] += p; };
             for (int q = 0; q < Q; q++) {
                 const double p = prow[q];
                 acc += p;
@@ -575,13 +578,13 @@ __device__ __forceinline__ void level_plain_body(const IT& it, unsigned char* s_
                 const uint8_t* rb = job.labels + job.ent_lab_off[e];
                 const int lr = job.ent_lab_len[e];
                 if (lr == 1) {
-                    if (ls == 1) hist[sb[0] * K + rb[0]] += p;
+                    if (ls == 1) add(sb[0], rb[0], p);
                 } else if (job.isnew[r]) {
                     int i = ls, j = lr;
-                    while (i > 0 && j > 0) { int a = sb[--i], b = rb[--j]; hist[a * K + b] += p; }
+                    while (i > 0 && j > 0) { const int a = sb[--i], b = rb[--j]; add(a, b, p); }
                 } else {
                     int i = 0, j = 0;
-                    while (i < ls && j < lr) { int a = sb[i++], b = rb[j++]; hist[a * K + b] += p; }
+                    while (i < ls && j < lr) { const int a = sb[i++], b = rb[j++]; add(a, b, p); }
                 }
             }
             R->abund[s] = acc;

@@ -25,7 +25,7 @@ def test_library_exports_header_symbols():
     from rambl_amd import capi
     lib = ctypes.CDLL(capi.LIB_PATH)
     names = declared_symbols()
-    assert len(names) >= 52 and "sc_profile_evalue6" in names and "sc_update_level" in names
+    assert len(names) >= 53 and "sc_profile_evalue6" in names and "sc_update_level" in names and "sc_hard_level" in names
     for n in names:
         assert hasattr(lib, n), n
     assert sorted(capi.EXPORTS) == names

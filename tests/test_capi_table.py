@@ -11,7 +11,7 @@ HEADER = os.path.join(ROOT, "include", "straincall_hip.h")
 RETURNS = {"int": C.c_int, "void": None, "long": C.c_long, "double": C.c_double, "const char*": C.c_char_p}
 SCALARS = {"int": C.c_int, "long": C.c_long, "double": C.c_double, "unsigned long long": C.c_ulonglong}
 POINTEES = dict(SCALARS, **{"unsigned": C.c_uint, "unsigned char": C.c_ubyte})
-N_DECLARED = 52         # the functions the header declares today (the library exports one more, sc_add_ones, which is no part of the ABI)
+N_DECLARED = 53         # the functions the header declares today (the library exports one more, sc_add_ones, which is no part of the ABI)
 
 
 def header_text():
