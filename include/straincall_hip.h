@@ -546,6 +546,59 @@ int sc_gene_pairs(int device, const char* gene_text, const long* gene_off, int n
 int sc_pairs_widths(int* widths, int cap);
 const char* sc_pairs_error(void);
 
+/* ---- a sample's reads mapped to the gene database on the device (rambl_amd/csrc/sc_map.hip) --------------
+ *
+ * scripts/get_sra_and_mapping.py:49-90 runs `bowtie2 --local -x <gene database>` and `samtools view -F4 -bht`, sort and index
+ * per sample.  Here a read's candidate genes come from k-mer votes, and the alignment is sc_align_reads' (§8.7) over them:
+ *   index       every window of seed_k bases (11..16) inside one gene, forward strand, ACGT only, is a key (code, gene); sorted
+ *   votes       v(r, g, s) = the windows of read r on strand s (1: its reverse complement), ACGT only, whose k-mer occurs in
+ *               gene g at least once; a k-mer whose run in the index has more than max_occ entries casts no vote;
+ *               v(r, g) = max over the strands
+ *   candidates  the genes with v(r, g) >= min_votes; when max_cand > 0 only the max_cand with the largest v, ties to the lower
+ *               gene index (max_cand == 0: all)
+ *   result      what sc_align_reads returns for r against its candidates in ascending gene order, `gene` being the index in
+ *               the database; a read without candidates has as 0, xs -1, gene -1
+ * Limits: reads of 1..512 bases, genes of 1..8192 bases, at most 1048575 genes, max_occ >= 1, max_cand >= 0, min_votes >= 1;
+ * anything else is SC_ERR_ARG or SC_ERR_UNSUPPORTED before any kernel is launched, with the message of the calling thread's
+ * last failure in sc_map_error().  The genes and their keys stay on the device of the index; one call at a time runs on an
+ * index.  Reads go through in stretches whose pairs fit pair_room (0: the library's default; a read that needs more on its
+ * own gets it); no result depends on the stretches. */
+typedef struct sc_map_index sc_map_index;
+struct sc_map_stats {
+    double index_ms;       /* HIP events: k_seed_keys and the sort, when the index was made */
+    double votes_ms;       /* HIP events: k_map_votes, the counting pass and the filling pass of every stretch */
+    double score_ms;       /* HIP events: k_sw_score_pairs, both strands of every (read, candidate) pair */
+    double trace_ms;       /* HIP events: k_sw_trace, one window per mapped read */
+    double total_ms;       /* wall time of the call, host packing included */
+    long n_keys;           /* keys of the index */
+    long n_windows;        /* ACGT windows of the reads, both strands counted, whose k-mer was looked up */
+    long n_skipped;        /* of those, the windows whose run has more than max_occ entries */
+    long n_pairs;          /* (read, candidate) pairs */
+    long score_cells;      /* DP cells of the score pass: sum of 2 * read length * gene length over the pairs */
+    long trace_cells;      /* DP cells the traceback pass swept */
+    long n_traced;         /* reads that mapped */
+    long n_stretches;      /* stretches the reads went through in */
+};
+typedef struct sc_map_stats sc_map_stats;
+/* get_sra_and_mapping.py:49-90, `bowtie2-build`: the genes to `device`, their keys made and sorted there. */
+int sc_map_index_create(int device, const char* gene_text, const long* gene_off, int n_genes, int seed_k, sc_map_index** index);
+/* get_sra_and_mapping.py:49-90: what an index holds (any pointer may be null). */
+int sc_map_index_info(const sc_map_index* index, int* n_genes, long* gene_bases, int* seed_k, long* n_keys, double* index_ms);
+void sc_map_index_free(sc_map_index* index);
+/* get_sra_and_mapping.py:49-90, `bowtie2 --local`: per read as, xs, gene, strand, pos, nm and the CIGAR as sc_align_reads
+ * returns them, and n_cand = the number of its candidates. */
+int sc_map_reads(sc_map_index* index, const char* read_text, const char* qual_text, const long* read_off, int n_reads, int max_occ,
+                 int max_cand, int min_votes, long pair_room, int* as, int* xs, int* gene, int* strand, int* pos, int* nm,
+                 unsigned* cigar, int cigar_stride, int* n_cigar, int* n_cand, sc_map_stats* stats);
+/* get_sra_and_mapping.py:49-90, a test and diagnostic entry: every read's candidates through the same two kernels, read r's at
+ * [cand_off[r], cand_off[r + 1]) in ascending gene order with the votes of both strands.  More than `cap`: SC_ERR_CAPACITY
+ * with *n_cand set to the number that suffices. */
+int sc_map_candidates(sc_map_index* index, const char* read_text, const long* read_off, int n_reads, int max_occ, int max_cand,
+                      int min_votes, long* cand_off, int* cand_gene, int* cand_fw, int* cand_rc, long cap, long* n_cand);
+/* get_sra_and_mapping.py:49-90: the genes one pass of the vote kernel counts in LDS and the most votes a pair can have. */
+int sc_map_limits(int* range_genes, int* max_votes);
+const char* sc_map_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,12 @@ class ScTaxaStats(Stats):
                 ("n_seqs", C.c_long), ("n_words", C.c_long), ("n_genera", C.c_long), ("table_bytes", C.c_long)]
 
 
+class ScMapStats(Stats):
+    _fields_ = [("index_ms", C.c_double), ("votes_ms", C.c_double), ("score_ms", C.c_double), ("trace_ms", C.c_double), ("total_ms", C.c_double),
+                ("n_keys", C.c_long), ("n_windows", C.c_long), ("n_skipped", C.c_long), ("n_pairs", C.c_long), ("score_cells", C.c_long),
+                ("trace_cells", C.c_long), ("n_traced", C.c_long), ("n_stretches", C.c_long)]
+
+
 class StrainCallError(RuntimeError):
     def __init__(self, code, msg=""):
         super().__init__("%s (%d)%s" % (ERRORS.get(code, "error"), code, (": " + msg) if msg else ""))
@@ -149,6 +155,13 @@ ENTRIES = [
     ("sc_gene_pairs", _i, [_i, _s, _lp, _i, _i, _i, _ip, _ip, _ip, _l, _lp, _dp, _i]),
     ("sc_pairs_widths", _i, [_ip, _i]),
     ("sc_pairs_error", _s, []),
+    ("sc_map_index_create", _i, [_i, _s, _lp, _i, _i, _vpp]),
+    ("sc_map_index_info", _i, [_vp, _ip, _lp, _ip, _lp, _dp]),
+    ("sc_map_index_free", None, [_vp]),
+    ("sc_map_reads", _i, [_vp, _s, _s, _lp, _i, _i, _i, _i, _l, _ip, _ip, _ip, _ip, _ip, _ip, _up, _i, _ip, _ip, _vp]),      # the last: a ScMapStats
+    ("sc_map_candidates", _i, [_vp, _s, _lp, _i, _i, _i, _i, _lp, _ip, _ip, _ip, _l, _lp]),
+    ("sc_map_limits", _i, [_ip, _ip]),
+    ("sc_map_error", _s, []),
 ]
 EXPORTS = [name for name, _, _ in ENTRIES]
 
@@ -914,3 +927,88 @@ class TaxaModel(Handle):
         rc = lib().sc_taxa_model_table(self._h, int(genus), _ptr(q))
         _check(rc, lib().sc_taxa_error)
         return q
+
+
+MAP_DEFAULTS = dict(seed_k=16, max_occ=1024, max_cand=16, min_votes=1)
+
+
+def map_limits():
+    """sc_map_limits (host only): (the genes one pass of the vote kernel counts in LDS, the most votes a pair can have)."""
+    rg, mv = C.c_int(), C.c_int()
+    _check(lib().sc_map_limits(C.byref(rg), C.byref(mv)))
+    return rg.value, mv.value
+
+
+class MapResult(AlignResult):
+    """AlignResult with `seed` the gene's index in the database (also as `gene`) and n_cand, the candidates of every read."""
+
+    def __init__(self, *fields, n_cand):
+        super().__init__(*fields)
+        self.gene, self.n_cand = self.seed, n_cand
+
+
+class MapIndex(Handle):
+    """The gene database of the read mapper held on one device until close() (sc_map_index_create): the
+    genes and their sorted k-mer keys.  genes: a list of bytes.  One call at a time."""
+    _free = "sc_map_index_free"
+
+    def __init__(self, genes, seed_k=MAP_DEFAULTS["seed_k"], device=0):
+        gtext, gl = _pack_long(genes)
+        self._h = C.c_void_p()
+        rc = lib().sc_map_index_create(int(device), gtext, _ptr(gl), len(genes), int(seed_k), C.byref(self._h))
+        _check(rc, lib().sc_map_error)
+
+    def info(self):
+        """sc_map_index_info: {"n_genes", "gene_bases", "seed_k", "n_keys", "index_ms"}."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        n_genes, bases, k, n_keys, ms = C.c_int(), C.c_long(), C.c_int(), C.c_long(), C.c_double()
+        rc = lib().sc_map_index_info(self._h, C.byref(n_genes), C.byref(bases), C.byref(k), C.byref(n_keys), C.byref(ms))
+        _check(rc, lib().sc_map_error)
+        return {"n_genes": n_genes.value, "gene_bases": bases.value, "seed_k": k.value, "n_keys": n_keys.value, "index_ms": ms.value}
+
+    def map_reads(self, reads, quals=None, max_occ=MAP_DEFAULTS["max_occ"], max_cand=MAP_DEFAULTS["max_cand"],
+                  min_votes=MAP_DEFAULTS["min_votes"], pair_room=0):
+        """sc_map_reads: every read against its candidate genes on both strands.  reads, quals: lists of bytes (quals None, or
+        an entry b"*": Q40).  Returns a MapResult."""
+        import numpy as np
+        if not self._h:
+            raise ValueError("the index is closed")
+        n = len(reads)
+        rtext, rl = _pack_long(reads)
+        qtext = None
+        if quals is not None:
+            qtext = b"".join(q if (q != b"*" and len(q) == len(r)) else b"I" * len(r) for r, q in zip(reads, quals))
+        stride = max([len(x) for x in reads] + [0]) // 2 + 4
+        as_, xs, gene, strand, pos, nm, ncig, ncand = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(8))
+        cig = np.zeros(max(n, 1) * stride, dtype=np.uint32)
+        st = ScMapStats()
+        rc = lib().sc_map_reads(self._h, rtext, qtext, _ptr(rl), n, int(max_occ), int(max_cand), int(min_votes), int(pair_room), _ptr(as_),
+                                _ptr(xs), _ptr(gene), _ptr(strand), _ptr(pos), _ptr(nm), _ptr(cig), stride, _ptr(ncig), _ptr(ncand), C.byref(st))
+        _check(rc, lib().sc_map_error)
+        cigars = []
+        for r in range(n):
+            ops = cig[r * stride:r * stride + ncig[r]]
+            cigars.append("".join("%d%s" % (int(v) >> 4, "MIDNSHP=X"[int(v) & 15]) for v in ops) if ncig[r] else "*")
+        return MapResult(as_[:n], xs[:n], gene[:n], strand[:n], pos[:n], nm[:n], cigars, st, n_cand=ncand[:n])
+
+    def candidates(self, reads, max_occ=MAP_DEFAULTS["max_occ"], max_cand=MAP_DEFAULTS["max_cand"], min_votes=MAP_DEFAULTS["min_votes"],
+                   cap=None):
+        """sc_map_candidates, a test and diagnostic entry: (cand_off[n + 1], gene, forward votes, reverse votes), read r's
+        candidates at [cand_off[r], cand_off[r + 1]) in ascending gene order.  The room starts at `cap` (default 65 536) and
+        grows to what the library asks for."""
+        import numpy as np
+        if not self._h:
+            raise ValueError("the index is closed")
+        rtext, rl = _pack_long(reads)
+        off = np.zeros(len(reads) + 1, dtype=np.int64)
+
+        def attempt(cap):
+            cols = [np.zeros(max(cap, 1), dtype=np.int32) for _ in range(3)]
+            n = C.c_long()
+            rc = lib().sc_map_candidates(self._h, rtext, _ptr(rl), len(reads), int(max_occ), int(max_cand), int(min_votes), _ptr(off),
+                                         *[_ptr(c) for c in cols], cap, C.byref(n))
+            return rc, n.value, cols
+        rc, k, cols = with_room(1 << 16 if cap is None else int(cap), attempt)
+        _check(rc, lib().sc_map_error)
+        return (off,) + tuple(c[:k] for c in cols)

@@ -56,20 +56,8 @@ struct BlCell {
     }
 };
 
-// Where a score kernel's tiles come from.  AllTiles: every bucket segment against every gene on both strands (tile_of).
-// PairTiles, the seeded mode: tile w is pair w >> 1 on strand w & 1, so a pair is always scored on both strands (the better
-// strand is picked before the filters; one strand alone could turn "no hit" into a hit).
-struct Pair { int seg, gene; };
-struct AllTiles {
-    int n_genes; const int* sids;
-    __device__ __forceinline__ Tile at(long w) const { return tile_of(w, n_genes, sids); }
-};
-struct PairTiles {
-    const Pair* pairs;
-    __device__ __forceinline__ Tile at(long w) const { const Pair p = pairs[w >> 1]; return Tile{p.seg, p.gene * 2 + (int)(w & 1)}; }
-};
-
-// One kernel for both: k_bl_score<R> is the full product, k_bl_score_pairs<R> the pair list.  The tile's body stays in the
+// One kernel for both tile sources of sc_wave_dp.hpp (AllTiles, and PairTiles for the seeded mode): k_bl_score<R> is the full
+// product, k_bl_score_pairs<R> the pair list.  The tile's body stays in the
 // kernel: as a function of (segment, gene, strand), and as a function holding the whole loop, it cost a register per lane at
 // R = 2..7 (the note at tile_of in sc_wave_dp.hpp says the same of its own case).
 template <int R, class Tiles>

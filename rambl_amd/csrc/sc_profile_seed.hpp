@@ -149,7 +149,7 @@ int lossless_k(int L, int min2, double min_identity_pct) {
 
 // The seed length of a call: the least k*(L) over the segment lengths present that can pass at all, at most SEED_MAX_K; 0
 // when it is below SEED_MIN_K (or no length can pass): the call runs unseeded.  *lossless: the bound before the clamps.
-int seed_length(const bool* has_len, long gene_bases, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, int* lossless) {
+inline int seed_length(const bool* has_len, long gene_bases, double min_identity_pct, double max_evalue, double ka_lambda, double ka_k, int* lossless) {
     int best = 0;
     for (int L = 1; L <= MAX_ROWS; L++) {
         if (!has_len[L]) continue;
@@ -200,7 +200,7 @@ struct SeedScratch {
 // per segment, scanned on the host into pair_off[sids.size() + 1], and -- unless their tiles are more than one call takes --
 // filled into sx.pairs in bucket order, genes ascending.  *score_cells (may be null) grows by 2 * segment length * gene length
 // per pair.  Returns the number of pairs; the stream is synchronised.
-long seed_pairs(sc::TimedStream& st, const SeedIndex& index, const long* d_go, int n_genes, const uint8_t* d_sq, const long* d_so,
+inline long seed_pairs(sc::TimedStream& st, const SeedIndex& index, const long* d_go, int n_genes, const uint8_t* d_sq, const long* d_so,
                 const Packed& sg, const Buckets& by_r, const std::vector<int>& sids, const int* d_sids, int seed_k, std::vector<long>& pair_off,
                 SeedScratch& sx, long* score_cells) {
     unsigned* d_cnt = sx.cnt.ensure(sids.size() + 1);

@@ -158,6 +158,20 @@ __device__ __forceinline__ Tile tile_of(long w, int n_refs, const int* ids) {
     return Tile{ids[ix], (int)(w - ix * 2L * n_refs)};
 }
 
+// Where a score kernel's tiles come from.  AllTiles: every bucket item against every reference on both strands (tile_of).
+// PairTiles: tile w is pair w >> 1 on strand w & 1, so a pair is always scored on both strands (the better strand is picked
+// before any filter; one strand alone could turn "no hit" into a hit).  `seg` is the row item of a pair, whatever the family
+// calls it.
+struct Pair { int seg, gene; };
+struct AllTiles {
+    int n_genes; const int* sids;
+    __device__ __forceinline__ Tile at(long w) const { return tile_of(w, n_genes, sids); }
+};
+struct PairTiles {
+    const Pair* pairs;
+    __device__ __forceinline__ Tile at(long w) const { const Pair p = pairs[w >> 1]; return Tile{p.seg, p.gene * 2 + (int)(w & 1)}; }
+};
+
 // The block loop of a traceback by one wavefront, the window's last block first:
 //     for (int b = last_block(ncol); b >= 0; b--) {
 //         const int colA = sweep_block<R, Cell>(ref, ncol, b, rw, nl, lane, bits);
