@@ -244,6 +244,12 @@ class Handle:
                 pass
             self._h = C.c_void_p()
 
+    def _open(self):
+        """The handle, for a call of the library; ValueError once it was given back."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        return self._h
+
     def __del__(self):
         self.close()
 
@@ -661,28 +667,41 @@ class AlignResult:
         self.as_, self.xs, self.seed, self.strand, self.pos, self.nm, self.cigar, self.stats = as_, xs, seed, strand, pos, nm, cigar, stats
 
 
-def align_reads(seeds, reads, quals=None, device=0):
-    """sc_align_reads: every read against every seed on both strands (stage 4, DESIGN.md §8.7).  seeds, reads, quals:
-    lists of bytes (quals None, or an entry b"*": Q40)."""
-    import numpy as np
-    n = len(reads)
-    stext, sl = _pack_long(seeds)
+def _read_args(reads, quals):
+    """What an alignment entry takes of the reads: (text, offsets, the qualities' text or None, the CIGAR stride).  quals
+    None: no qualities; an entry b"*", or one of another length than its read, is Q40 throughout."""
     rtext, rl = _pack_long(reads)
     qtext = None
     if quals is not None:
         qtext = b"".join(q if (q != b"*" and len(q) == len(r)) else b"I" * len(r) for r, q in zip(reads, quals))
-    stride = max([len(x) for x in reads] + [0]) // 2 + 4
-    as_, xs, seed, strand, pos, nm, ncig = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(7))
-    cig = np.zeros(max(n, 1) * stride, dtype=np.uint32)
+    return rtext, rl, qtext, max([len(x) for x in reads] + [0]) // 2 + 4
+
+
+def _align_out(n, stride):
+    """The arrays an alignment entry fills for n reads: (as, xs, seed, strand, pos, nm), the CIGAR words, their counts."""
+    import numpy as np
+    cols = [np.zeros(max(n, 1), dtype=np.int32) for _ in range(6)]
+    return cols, np.zeros(max(n, 1) * stride, dtype=np.uint32), np.zeros(max(n, 1), dtype=np.int32)
+
+
+def _cigar_texts(cig, ncig, stride, n):
+    """The CIGAR text of each of n reads from its ncig[r] words (length << 4 | op) at cig[r * stride]; "*" for none."""
+    return ["".join("%d%s" % (int(v) >> 4, "MIDNSHP=X"[int(v) & 15]) for v in cig[r * stride:r * stride + ncig[r]]) if ncig[r] else "*"
+            for r in range(n)]
+
+
+def align_reads(seeds, reads, quals=None, device=0):
+    """sc_align_reads: every read against every seed on both strands (stage 4, DESIGN.md §8.7).  seeds, reads, quals:
+    lists of bytes (quals None, or an entry b"*": Q40)."""
+    n = len(reads)
+    stext, sl = _pack_long(seeds)
+    rtext, rl, qtext, stride = _read_args(reads, quals)
+    cols, cig, ncig = _align_out(n, stride)
     st = ScAlignStats()
-    rc = lib().sc_align_reads(device, stext, _ptr(sl), len(seeds), rtext, qtext, _ptr(rl), n, _ptr(as_), _ptr(xs), _ptr(seed), _ptr(strand),
-                              _ptr(pos), _ptr(nm), _ptr(cig), stride, _ptr(ncig), C.byref(st))
+    rc = lib().sc_align_reads(device, stext, _ptr(sl), len(seeds), rtext, qtext, _ptr(rl), n, *[_ptr(c) for c in cols], _ptr(cig), stride,
+                              _ptr(ncig), C.byref(st))
     _check(rc, lib().sc_align_error)
-    cigars = []
-    for r in range(n):
-        ops = cig[r * stride:r * stride + ncig[r]]
-        cigars.append("".join("%d%s" % (int(v) >> 4, "MIDNSHP=X"[int(v) & 15]) for v in ops) if ncig[r] else "*")
-    return AlignResult(as_[:n], xs[:n], seed[:n], strand[:n], pos[:n], nm[:n], cigars, st)
+    return AlignResult(*[c[:n] for c in cols], _cigar_texts(cig, ncig, stride, n), st)
 
 
 class ProfileHits:
@@ -840,10 +859,8 @@ class ProfileIndex(Handle):
 
     def info(self):
         """sc_profile_index_info: {"n_genes", "gene_bases", "cached_k": the seed lengths whose keys are kept, ascending}."""
-        if not self._h:
-            raise ValueError("the index is closed")
         n_genes, bases, n_k, ks = C.c_int(), C.c_long(), C.c_int(), (C.c_int * 6)()
-        rc = lib().sc_profile_index_info(self._h, C.byref(n_genes), C.byref(bases), C.byref(n_k), ks)
+        rc = lib().sc_profile_index_info(self._open(), C.byref(n_genes), C.byref(bases), C.byref(n_k), ks)
         _check(rc, lib().sc_profile_error)
         return {"n_genes": n_genes.value, "gene_bases": bases.value, "cached_k": [int(ks[i]) for i in range(n_k.value)]}
 
@@ -853,8 +870,7 @@ class ProfileIndex(Handle):
         one read index per segment; read_sample: the sample (0..n_samples-1) of every read, non-decreasing.  The room for rows
         starts at `cap` (default 65 536) and grows to what the library asks for.  Returns a ProfileCohortCounts."""
         import numpy as np
-        if not self._h:
-            raise ValueError("the index is closed")
+        h = self._open()
         samples = np.ascontiguousarray(read_sample, dtype=np.int32)
 
         def read_args(reads):
@@ -862,7 +878,7 @@ class ProfileIndex(Handle):
                 raise ValueError("read %d of %d reads with a sample" % (int(reads.max()), len(samples)))
             return [len(samples), _ptr(samples), int(n_samples)]
         options = (float(min_identity), float(max_evalue), float(ka_lambda), float(ka_k), int(bool(seeded)), int(cand_room))
-        return ProfileCohortCounts(*_count_rows(lib().sc_profile_index_counts, (self._h,), segs, seg_read, read_args, options, cap, 4,
+        return ProfileCohortCounts(*_count_rows(lib().sc_profile_index_counts, (h,), segs, seg_read, read_args, options, cap, 4,
                                                 ScProfileCohortStats))
 
 
@@ -960,10 +976,8 @@ class MapIndex(Handle):
 
     def info(self):
         """sc_map_index_info: {"n_genes", "gene_bases", "seed_k", "n_keys", "index_ms"}."""
-        if not self._h:
-            raise ValueError("the index is closed")
         n_genes, bases, k, n_keys, ms = C.c_int(), C.c_long(), C.c_int(), C.c_long(), C.c_double()
-        rc = lib().sc_map_index_info(self._h, C.byref(n_genes), C.byref(bases), C.byref(k), C.byref(n_keys), C.byref(ms))
+        rc = lib().sc_map_index_info(self._open(), C.byref(n_genes), C.byref(bases), C.byref(k), C.byref(n_keys), C.byref(ms))
         _check(rc, lib().sc_map_error)
         return {"n_genes": n_genes.value, "gene_bases": bases.value, "seed_k": k.value, "n_keys": n_keys.value, "index_ms": ms.value}
 
@@ -972,25 +986,16 @@ class MapIndex(Handle):
         """sc_map_reads: every read against its candidate genes on both strands.  reads, quals: lists of bytes (quals None, or
         an entry b"*": Q40).  Returns a MapResult."""
         import numpy as np
-        if not self._h:
-            raise ValueError("the index is closed")
+        h = self._open()
         n = len(reads)
-        rtext, rl = _pack_long(reads)
-        qtext = None
-        if quals is not None:
-            qtext = b"".join(q if (q != b"*" and len(q) == len(r)) else b"I" * len(r) for r, q in zip(reads, quals))
-        stride = max([len(x) for x in reads] + [0]) // 2 + 4
-        as_, xs, gene, strand, pos, nm, ncig, ncand = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(8))
-        cig = np.zeros(max(n, 1) * stride, dtype=np.uint32)
+        rtext, rl, qtext, stride = _read_args(reads, quals)
+        cols, cig, ncig = _align_out(n, stride)
+        ncand = np.zeros(max(n, 1), dtype=np.int32)
         st = ScMapStats()
-        rc = lib().sc_map_reads(self._h, rtext, qtext, _ptr(rl), n, int(max_occ), int(max_cand), int(min_votes), int(pair_room), _ptr(as_),
-                                _ptr(xs), _ptr(gene), _ptr(strand), _ptr(pos), _ptr(nm), _ptr(cig), stride, _ptr(ncig), _ptr(ncand), C.byref(st))
+        rc = lib().sc_map_reads(h, rtext, qtext, _ptr(rl), n, int(max_occ), int(max_cand), int(min_votes), int(pair_room),
+                                *[_ptr(c) for c in cols], _ptr(cig), stride, _ptr(ncig), _ptr(ncand), C.byref(st))
         _check(rc, lib().sc_map_error)
-        cigars = []
-        for r in range(n):
-            ops = cig[r * stride:r * stride + ncig[r]]
-            cigars.append("".join("%d%s" % (int(v) >> 4, "MIDNSHP=X"[int(v) & 15]) for v in ops) if ncig[r] else "*")
-        return MapResult(as_[:n], xs[:n], gene[:n], strand[:n], pos[:n], nm[:n], cigars, st, n_cand=ncand[:n])
+        return MapResult(*[c[:n] for c in cols], _cigar_texts(cig, ncig, stride, n), st, n_cand=ncand[:n])
 
     def candidates(self, reads, max_occ=MAP_DEFAULTS["max_occ"], max_cand=MAP_DEFAULTS["max_cand"], min_votes=MAP_DEFAULTS["min_votes"],
                    cap=None):
@@ -998,15 +1003,14 @@ class MapIndex(Handle):
         candidates at [cand_off[r], cand_off[r + 1]) in ascending gene order.  The room starts at `cap` (default 65 536) and
         grows to what the library asks for."""
         import numpy as np
-        if not self._h:
-            raise ValueError("the index is closed")
+        h = self._open()
         rtext, rl = _pack_long(reads)
         off = np.zeros(len(reads) + 1, dtype=np.int64)
 
         def attempt(cap):
             cols = [np.zeros(max(cap, 1), dtype=np.int32) for _ in range(3)]
             n = C.c_long()
-            rc = lib().sc_map_candidates(self._h, rtext, _ptr(rl), len(reads), int(max_occ), int(max_cand), int(min_votes), _ptr(off),
+            rc = lib().sc_map_candidates(h, rtext, _ptr(rl), len(reads), int(max_occ), int(max_cand), int(min_votes), _ptr(off),
                                          *[_ptr(c) for c in cols], cap, C.byref(n))
             return rc, n.value, cols
         rc, k, cols = with_room(1 << 16 if cap is None else int(cap), attempt)

@@ -140,10 +140,12 @@ template <class T> struct PinMem {                        // page-locked host me
     ~PinMem() { (void)hipHostFree(p); }
 };
 // A stream of one call with the events that time its phases: mark(name) records one where the stream stands, ms(a, b) is
-// the device time between two of them once the stream was synchronised.  Copies of no bytes are left out.
+// the device time between two of them once the stream was synchronised.  A phase that recurs is a span: span(name, body)
+// records an event before and after what body enqueues, as often as it is called, and span_ms(name) is the sum of the
+// device times of that name's pairs.  Copies of no bytes are left out.
 struct TimedStream {
     Stream s;
-    std::vector<std::pair<const char*, hipEvent_t>> marks;
+    std::vector<std::pair<const char*, hipEvent_t>> marks;      // the marks of a span's name alternate: begin, end
     ~TimedStream() { for (auto& m : marks) (void)hipEventDestroy(m.second); }
     operator hipStream_t() const { return s.st; }
     void mark(const char* name) {
@@ -152,9 +154,20 @@ struct TimedStream {
         marks.emplace_back(name, e);
         HIPCHK(hipEventRecord(e, s.st));
     }
-    float ms(const char* a, const char* b) const {
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, event(a), event(b)));
+    float ms(const char* a, const char* b) const { return elapsed(event(a), event(b)); }
+    template <class F> void span(const char* name, F&& body) {
+        mark(name);
+        body();
+        mark(name);
+    }
+    double span_ms(const char* name) const {
+        double t = 0;
+        hipEvent_t begin = nullptr;
+        for (auto& m : marks) {
+            if (strcmp(m.first, name)) continue;
+            if (begin) t += elapsed(begin, m.second);
+            begin = begin ? nullptr : m.second;
+        }
         return t;
     }
     void h2d(void* dst, const void* src, size_t n) { if (n) HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s.st)); }
@@ -166,6 +179,11 @@ struct TimedStream {
     void sync() { HIPCHK(hipStreamSynchronize(s.st)); }
 
 private:
+    static float elapsed(hipEvent_t a, hipEvent_t b) {
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, a, b));
+        return t;
+    }
     hipEvent_t event(const char* name) const {
         for (auto& m : marks) if (!strcmp(m.first, name)) return m.second;
         throw HipError(std::string("no mark ") + name);

@@ -6,7 +6,6 @@
 //   * the entry points: the reads go through the counting pass at once and through the filling pass and k_sw_score_pairs in
 //     stretches whose pairs fit the room; k_sw_trace runs once over the reads that mapped.
 #include <cstring>
-#include <deque>
 #include <memory>
 
 #include "sc_profile_seed.hpp"
@@ -25,6 +24,7 @@ static_assert(MAP_MAX_VOTES == MAX_ROWS - SEED_MIN_K + 1 && MAP_MAX_VOTES < MAP_
 // order.  Without a cut (max_cand == 0, or no more genes than max_cand) t = min_votes - 1 and keep = 0.
 struct Cut { int t, keep; };
 enum { TALLY_WINDOWS, TALLY_SKIPPED, TALLY_CELLS, N_TALLY };
+constexpr const char *VOTES = "votes", *SCORE = "score";      // the spans of a call's stream that sc_map_stats sums
 
 // One wavefront per read of `rids`.  A lane takes a stretch of the read's windows and rolls both codes along it (the pattern
 // of k_seed_lookup); the genes are gone over in ranges of MAP_RANGE, and per range the lane walks every window's run of the
@@ -172,28 +172,6 @@ __global__ __launch_bounds__(64) void k_map_votes(const unsigned long long* keys
 
 thread_local sc::LastError tl_error;
 
-// The spans of a call's phases on its stream: several per phase, summed.
-struct Phases {
-    enum { VOTES, SCORE, N };
-    std::deque<std::string> names;
-    std::vector<std::pair<const char*, const char*>> spans[N];
-    template <class F> void span(sc::TimedStream& st, int phase, F&& body) {
-        names.push_back("a" + std::to_string(names.size()));
-        const char* a = names.back().c_str();
-        st.mark(a);
-        body();
-        names.push_back("b" + std::to_string(names.size()));
-        const char* b = names.back().c_str();
-        st.mark(b);
-        spans[phase].emplace_back(a, b);
-    }
-    double ms(const sc::TimedStream& st, int phase) const {
-        double t = 0;
-        for (auto& ab : spans[phase]) t += st.ms(ab.first, ab.second);
-        return t;
-    }
-};
-
 }  // namespace
 
 // The handle of sc_map_index_create: the genes and their sorted keys on one device, and the arrays the calls work in, kept
@@ -263,7 +241,7 @@ void launch_votes(sc::TimedStream& st, sc_map_index& ix, const Front& f, long at
 
 // Packs and uploads the reads (rd rebased, ids set) and runs the counting pass; poff is then the scan of the counts and lies
 // on the device too.  n_cand (may be null): the count of every read, by read.  The stream is synchronised.
-void count_candidates(sc::TimedStream& st, Phases& ph, sc_map_index& ix, Front& f, const char* read_text, const char* qual_text, int max_occ,
+void count_candidates(sc::TimedStream& st, sc_map_index& ix, Front& f, const char* read_text, const char* qual_text, int max_occ,
                       int max_cand, int min_votes, int* n_cand) {
     const size_t n = f.ids.size();
     f.rd.pack(read_text, [&](long k, int c) { return read_row_byte(c, qual_text, k); });
@@ -278,7 +256,7 @@ void count_candidates(sc::TimedStream& st, Phases& ph, sc_map_index& ix, Front& 
     st.h2d(f.d_ro, f.rd.off.data(), (n + 1) * sizeof(long));
     st.h2d(f.d_ids, f.ids.data(), n * sizeof(int));
     st.zero(f.d_tally, N_TALLY * sizeof(unsigned long long));
-    ph.span(st, Phases::VOTES, [&] { launch_votes<false>(st, ix, f, 0, (int)n, max_occ, max_cand, min_votes, 0, nullptr, nullptr); });
+    st.span(VOTES, [&] { launch_votes<false>(st, ix, f, 0, (int)n, max_occ, max_cand, min_votes, 0, nullptr, nullptr); });
     std::vector<unsigned> cnt(n);
     st.d2h(cnt.data(), f.d_cnt, n * sizeof(unsigned));
     st.sync();
@@ -354,8 +332,7 @@ int sc_map_candidates(sc_map_index* index, const char* read_text, const long* re
         sc_map_index& ix = *index;
         for (int r = 0; r < n_reads; r++) f.ids.push_back(r);
         sc::TimedStream st;
-        Phases ph;
-        count_candidates(st, ph, ix, f, read_text + read_off[0], nullptr, max_occ, max_cand, min_votes, nullptr);
+        count_candidates(st, ix, f, read_text + read_off[0], nullptr, max_occ, max_cand, min_votes, nullptr);
         const long total = f.poff.back();
         *n_cand = total;
         std::copy(f.poff.begin(), f.poff.end(), cand_off);
@@ -403,8 +380,7 @@ int sc_map_reads(sc_map_index* index, const char* read_text, const char* qual_te
         for (int r = 0; r < n_reads; r++) by_r.add(r, f.rd.len(r));
         f.ids = by_r.order();
         sc::TimedStream st;
-        Phases ph;
-        count_candidates(st, ph, ix, f, read_text + read_off[0], qual_text ? qual_text + read_off[0] : nullptr, max_occ, max_cand, min_votes,
+        count_candidates(st, ix, f, read_text + read_off[0], qual_text ? qual_text + read_off[0] : nullptr, max_occ, max_cand, min_votes,
                          n_cand);
         unsigned long long* d_best = ix.best.ensure((size_t)n_reads);
         unsigned long long* d_second = ix.second.ensure((size_t)n_reads);
@@ -424,8 +400,8 @@ int sc_map_reads(sc_map_index* index, const char* read_text, const char* qual_te
         for (size_t c = 0; c + 1 < cuts.size(); c++) {
             const long a = cuts[c], b = cuts[c + 1], base = f.poff[(size_t)a];
             if (f.poff[(size_t)b] == base) continue;
-            ph.span(st, Phases::VOTES, [&] { launch_votes<true>(st, ix, f, a, (int)(b - a), max_occ, max_cand, min_votes, base, d_pairs, nullptr); });
-            ph.span(st, Phases::SCORE, [&] {
+            st.span(VOTES, [&] { launch_votes<true>(st, ix, f, a, (int)(b - a), max_occ, max_cand, min_votes, base, d_pairs, nullptr); });
+            st.span(SCORE, [&] {
                 by_r.each([&](auto r, long at, const std::vector<int>& ids) {
                     const long lo = std::max(a, at), hi = std::min(b, at + (long)ids.size());
                     if (lo >= hi) return;
@@ -448,8 +424,8 @@ int sc_map_reads(sc_map_index* index, const char* read_text, const char* qual_te
         if (n_tr < 0) rc = tl_error.fail(SC_ERR_INTERNAL, fn + ": traceback of read " + std::to_string(-1 - n_tr) + " failed");
         if (stats && rc == SC_OK) {
             stats->index_ms = ix.index_ms;
-            stats->votes_ms = ph.ms(st, Phases::VOTES);
-            stats->score_ms = ph.ms(st, Phases::SCORE);
+            stats->votes_ms = st.span_ms(VOTES);
+            stats->score_ms = st.span_ms(SCORE);
             stats->trace_ms = st.ms("trace", "traced");
             stats->n_keys = (long)ix.seeds->n_keys;
             stats->n_windows = (long)tally[TALLY_WINDOWS];

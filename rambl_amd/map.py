@@ -13,8 +13,8 @@ import logging
 import os
 import sys
 
-from . import capi
-from .stage4 import _ref_len, revcomp
+from . import capi, samio
+from .samio import sam_header  # noqa: F401  (a name of this module)
 
 MAX_READ = 512
 MAX_GENE = 8192
@@ -67,7 +67,6 @@ def read_fastq(path):
 
 def read_genes(path):
     """(names, sequences as bytes) of the gene FASTA in file order."""
-    from . import samio
     try:
         fa = samio.Fasta(path)
     except OSError as e:
@@ -120,49 +119,11 @@ def map_sample(index, sample, max_occ, max_cand, min_votes, pair_room=0):
     return out, len(flat) - len(take), res.stats
 
 
-def sam_header(names, seqs):
-    """What `samtools view -ht <fai>` and `sort` leave: one @SQ per gene of the FASTA, in FASTA order."""
-    return "@HD\tVN:1.0\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(names, seqs))
-
-
 def sam_records(sample, res, names):
     """The SAM lines of the mapped reads (-F4), sorted by (gene index, POS) stably over input order, mate 1 before mate 2.  A
     mapped read whose mate did not map is kept, with 0x8, RNEXT * and PNEXT 0."""
-    recs = []
-    k = 0
-    for q, mates in sample:
-        idx = list(range(k, k + len(mates)))
-        k += len(mates)
-        for m, i in enumerate(idx):
-            if res.gene[i] < 0:
-                continue
-            seq, qual = mates[m]
-            rev = res.strand[i]
-            flag = 0x10 if rev else 0
-            rnext, pnext, tlen = "*", 0, 0
-            if len(mates) == 2:
-                o = idx[1 - m]
-                flag |= 0x1 | (0x40 if m == 0 else 0x80)
-                if res.gene[o] < 0:
-                    flag |= 0x8
-                else:
-                    flag |= 0x20 if res.strand[o] else 0
-                    pnext = res.pos[o]
-                    rnext = "=" if res.gene[o] == res.gene[i] else names[res.gene[o]]
-                    if res.gene[o] == res.gene[i]:
-                        a0, a1 = res.pos[i], res.pos[i] + _ref_len(res.cigar[i]) - 1
-                        b0, b1 = res.pos[o], res.pos[o] + _ref_len(res.cigar[o]) - 1
-                        span = max(a1, b1) - min(a0, b0) + 1
-                        tlen = span if (a0 < b0 or (a0 == b0 and m == 0)) else -span
-            if rev:
-                seq, qual = revcomp(seq), qual[::-1]
-            tags = "AS:i:%d" % res.as_[i] + ("\tXS:i:%d" % res.xs[i] if res.xs[i] >= 0 else "") + "\tNM:i:%d" % res.nm[i]
-            line = "%s\t%d\t%s\t%d\t%d\t%s\t%s\t%d\t%d\t%s\t%s\t%s\n" % (
-                q.decode(), flag, names[res.gene[i]], res.pos[i], 0 if res.xs[i] == res.as_[i] else 42, res.cigar[i], rnext, pnext, tlen,
-                seq.decode(), qual.decode(), tags)
-            recs.append(((res.gene[i], res.pos[i]), line))
-    recs.sort(key=lambda r: r[0])                     # stable: input order, mate 1 before mate 2, stays inside a key
-    return [r[1] for r in recs]
+    return samio.sam_records(sample, res.gene, res.strand, res.pos, res.as_, res.xs, res.nm, res.cigar, names,
+                             keep_lone_mate=True, sort_by_strand=False)
 
 
 def parse_args(argv):

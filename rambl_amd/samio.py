@@ -8,6 +8,9 @@ text it is, and the mapping file (SAM text or BAM) is read once by the library
 text) -- no subprocess, no temp files.  Parity at the samtools boundary itself stays unpinned
 (SURVEY.md section 8(c)); the emulation of the tool's TEXT that the tests compare the reader
 with is tests/py_ingest_mirror.py.
+
+The SAM text the package writes itself (stage 4's re-clustered reads, the read mapper's sample) comes from sam_header and
+sam_records below; the two callers differ in two policies that sam_records takes as arguments.
 """
 
 
@@ -67,6 +70,78 @@ def read_fai(path):
             if fld:
                 out.append((fld[0], fld[1] if len(fld) > 1 else ""))
     return out
+
+
+_COMP = bytes.maketrans(b"ACGTNacgtn", b"TGCANtgcan")
+
+
+def revcomp(seq):
+    return seq.translate(_COMP)[::-1]
+
+
+def ref_len(cigar):
+    """The reference bases a CIGAR text covers."""
+    n, v = 0, 0
+    for ch in cigar:
+        if ch.isdigit():
+            v = v * 10 + ord(ch) - 48
+        else:
+            if ch in "MD=XN":
+                n += v
+            v = 0
+    return n
+
+
+def sam_header(names, seqs):
+    """@HD with SO:coordinate and one @SQ per reference, in the given order."""
+    return "@HD\tVN:1.0\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(names, seqs))
+
+
+def sam_records(reads, ref, strand, pos, as_, xs, nm, cigar, names, keep_lone_mate, sort_by_strand):
+    """The SAM lines of the aligned reads of `reads`, [(QNAME, [(SEQ, QUAL), ...])] with one or two mates per entry.  ref,
+    strand, pos, as_, xs, nm and cigar hold one value per read entry of `reads` flattened (a pair's mates one after the
+    other), as numpy arrays or lists: ref is the index into `names` (-1: unaligned, and no line), pos is 1-based, xs < 0
+    means none.  MAPQ is 0 when XS = AS and 42 otherwise; a reverse read is written reverse-complemented.
+    keep_lone_mate: an aligned read whose mate is unaligned is kept, with 0x8, RNEXT * and PNEXT 0 (False: the pair is dropped).
+    sort_by_strand: the lines are sorted by (reference, POS, reverse) (False: by (reference, POS)), stably over the order
+    of `reads`, mate 1 before mate 2."""
+    ref, strand, pos = [int(v) for v in ref], [int(v) for v in strand], [int(v) for v in pos]
+    recs = []
+    k = 0
+    for q, mates in reads:
+        idx = list(range(k, k + len(mates)))
+        k += len(mates)
+        if not keep_lone_mate and any(ref[i] < 0 for i in idx):
+            continue
+        for m, i in enumerate(idx):
+            if ref[i] < 0:
+                continue
+            seq, qual = mates[m]
+            flag = 0x10 if strand[i] else 0
+            rnext, pnext, tlen = "*", 0, 0
+            if len(mates) == 2:
+                o = idx[1 - m]
+                flag |= 0x1 | (0x40 if m == 0 else 0x80)
+                if ref[o] < 0:
+                    flag |= 0x8
+                else:
+                    flag |= 0x20 if strand[o] else 0
+                    pnext = pos[o]
+                    rnext = "=" if ref[o] == ref[i] else names[ref[o]]
+                    if ref[o] == ref[i]:
+                        a0, a1 = pos[i], pos[i] + ref_len(cigar[i]) - 1
+                        b0, b1 = pos[o], pos[o] + ref_len(cigar[o]) - 1
+                        span = max(a1, b1) - min(a0, b0) + 1
+                        tlen = span if (a0 < b0 or (a0 == b0 and m == 0)) else -span
+            if strand[i]:
+                seq, qual = revcomp(seq), qual[::-1]          # a quality of * stays *
+            a, x = int(as_[i]), int(xs[i])
+            tags = "AS:i:%d" % a + ("\tXS:i:%d" % x if x >= 0 else "") + "\tNM:i:%d" % int(nm[i])
+            line = "%s\t%d\t%s\t%d\t%d\t%s\t%s\t%d\t%d\t%s\t%s\t%s\n" % (
+                q.decode(), flag, names[ref[i]], pos[i], 0 if x == a else 42, cigar[i], rnext, pnext, tlen, seq.decode(), qual.decode(), tags)
+            recs.append(((ref[i], pos[i], strand[i] if sort_by_strand else 0), line))
+    recs.sort(key=lambda r: r[0])                     # stable: input order, mate 1 before mate 2, stays inside a key
+    return [r[1] for r in recs]
 
 
 class Alignments:

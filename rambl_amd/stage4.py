@@ -10,15 +10,11 @@ result is written as SAM text, which stage 5 (rambl_amd/stage5.py, bin/StrainCal
 import math
 import os
 
-from . import capi
+from . import capi, samio
+from .samio import revcomp, sam_header  # noqa: F401  (names of this module)
 
 MAPPER = "bowtie2"
 MAP_ARGS = "--sensitive-local"
-_COMP = bytes.maketrans(b"ACGTNacgtn", b"TGCANtgcan")
-
-
-def revcomp(seq):
-    return seq.translate(_COMP)[::-1]
 
 
 def threshold(n):
@@ -72,7 +68,6 @@ def extract_reads(records):
 def write_seed_fasta(gene_fasta, seeds, path, width=60):
     """`samtools faidx GENE_FASTA seeds... > path` and `samtools faidx path`: the seed records in seed-list order with
     60-column lines, and the .fai (name, length, offset, line bases, line bytes)."""
-    from . import samio
     fa = samio.Fasta(gene_fasta)
     missing = [s for s in seeds if s not in fa.seqs]
     if missing:
@@ -91,60 +86,12 @@ def write_seed_fasta(gene_fasta, seeds, path, width=60):
     return seqs
 
 
-def _ref_len(cigar):
-    n, v = 0, 0
-    for ch in cigar:
-        if ch.isdigit():
-            v = v * 10 + ord(ch) - 48
-        else:
-            if ch in "MD=XN":
-                n += v
-            v = 0
-    return n
-
-
 def sam_records(reads, res, seed_names):
     """The SAM lines of the aligned reads in the contract's order: reads that do not align and pairs with a mate that does
     not align are dropped (-F1804), the rest sorted by (seed, POS, reverse) stably over QNAME order, mate 1 before mate 2.
     `res` holds one alignment per read entry of `reads` flattened (a pair's mates one after the other)."""
-    recs = []
-    k = 0
-    for q, mates in reads:
-        idx = list(range(k, k + len(mates)))
-        k += len(mates)
-        if any(res.seed[i] < 0 for i in idx):
-            continue
-        for m, i in enumerate(idx):
-            seq, qual = mates[m]
-            rev = int(res.strand[i])
-            flag = 0x10 if rev else 0
-            rnext, pnext, tlen = "*", 0, 0
-            if len(mates) == 2:
-                o = idx[1 - m]
-                flag |= 0x1 | (0x40 if m == 0 else 0x80) | (0x20 if res.strand[o] else 0)
-                pnext = int(res.pos[o])
-                rnext = "=" if res.seed[o] == res.seed[i] else seed_names[res.seed[o]]
-                if res.seed[o] == res.seed[i]:
-                    a0, a1 = int(res.pos[i]), int(res.pos[i]) + _ref_len(res.cigar[i]) - 1
-                    b0, b1 = int(res.pos[o]), int(res.pos[o]) + _ref_len(res.cigar[o]) - 1
-                    span = max(a1, b1) - min(a0, b0) + 1
-                    left = a0 < b0 or (a0 == b0 and m == 0)
-                    tlen = span if left else -span
-            if rev:
-                seq = revcomp(seq)
-                qual = qual if qual == b"*" else qual[::-1]
-            as_, xs = int(res.as_[i]), int(res.xs[i])
-            tags = "AS:i:%d" % as_ + ("\tXS:i:%d" % xs if xs >= 0 else "") + "\tNM:i:%d" % int(res.nm[i])
-            line = "%s\t%d\t%s\t%d\t%d\t%s\t%s\t%d\t%d\t%s\t%s\t%s\n" % (
-                q.decode(), flag, seed_names[res.seed[i]], int(res.pos[i]), 0 if xs == as_ else 42, res.cigar[i], rnext, pnext, tlen,
-                seq.decode(), qual.decode(), tags)
-            recs.append(((int(res.seed[i]), int(res.pos[i]), rev), line))
-    recs.sort(key=lambda r: r[0])                     # stable: QNAME order, mate 1 before mate 2, stays inside a key
-    return [r[1] for r in recs]
-
-
-def sam_header(seed_names, seed_seqs):
-    return "@HD\tVN:1.0\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(seed_names, seed_seqs))
+    return samio.sam_records(reads, res.seed, res.strand, res.pos, res.as_, res.xs, res.nm, res.cigar, seed_names,
+                             keep_lone_mate=False, sort_by_strand=True)
 
 
 def recluster(gene_fasta, seed_file, bam_file, out_dir=".", mapper=MAPPER, map_args=MAP_ARGS, device=0, verbose=False, alns=None):

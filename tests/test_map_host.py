@@ -184,6 +184,48 @@ def test_sam_flags_order_and_header():
     assert by[("p1", 0x80)][11:] == ["AS:i:18", "XS:i:18", "NM:i:1"] and by[("p1", 0x40)][11:] == ["AS:i:20", "NM:i:0"]
 
 
+def test_shared_sam_writer_policies_differ_only_as_stated():
+    """samio.sam_records under stage 4's policies (a pair with an unaligned mate dropped, the strand in the sort key) and the
+    mapper's (the aligned mate kept with 0x8, sorted by reference and POS alone) on one input: the two texts differ in that
+    pair and in the order of two records of one POS, and nowhere else; numpy arrays and lists give the same text."""
+    import numpy as np
+    from rambl_amd import samio
+    names = ["gA", "gB"]
+    reads = [(b"lone", [(b"ACGTACGTAC", b"IIIIIIIII#"), (b"TTGACCATGA", b"#IIIIIIIII")]),      # mate 2 unaligned
+             (b"same", [(b"ACGTTGCAAC", b"ABCDEFGHIJ"), (b"GGATCCAATT", b"JIHGFEDCBA")]),      # one POS, mate 1 reverse, mate 2 forward
+             (b"star", [(b"AACCGGTTAC", b"*")]),                                             # reverse, no qualities
+             (b"last", [(b"ACGTACGTAC", b"IIIIIIIIII")])]
+    cols = dict(ref=[0, -1, 1, 1, 0, 1], strand=[0, 0, 1, 0, 1, 0], pos=[40, 0, 20, 20, 7, 90], as_=[20, 0, 20, 18, 16, 20],
+                xs=[-1, -1, 18, 18, -1, 20], nm=[0, 0, 0, 1, 2, 0])
+    cigar = ["10M", "*", "10M", "4M1D6M", "2S8M", "10M"]
+
+    def text(keep, by_strand, arrays):
+        c = {k: np.array(v, dtype=np.int32) for k, v in cols.items()} if arrays else cols
+        return samio.sam_records(reads, c["ref"], c["strand"], c["pos"], c["as_"], c["xs"], c["nm"], cigar, names, keep, by_strand)
+    stage4, mapper = text(False, True, True), text(True, False, False)
+    assert stage4 == text(False, True, False) and mapper == text(True, False, True)
+    # the pair with the unaligned mate
+    lone = [x for x in mapper if x.startswith("lone\t")]
+    assert not any(x.startswith("lone\t") for x in stage4) and len(lone) == 1
+    f = lone[0].split("\t")
+    assert int(f[1]) == 0x1 | 0x40 | 0x8 and f[2:4] == ["gA", "40"] and f[6:9] == ["*", "0", "0"]
+    # the two records of one POS: forward before reverse under stage 4's key, input order (mate 1, the reverse one) under the mapper's
+    def flags(lines):
+        return [int(x.split("\t")[1]) for x in lines if x.startswith("same\t")]
+    assert flags(stage4) == [0x1 | 0x80 | 0x20, 0x1 | 0x40 | 0x10] and flags(mapper) == flags(stage4)[::-1]
+    # every other line, and its place
+    rest = [x for x in mapper if not x.startswith("lone\t")]
+    a, b = (k for k, x in enumerate(rest) if x.startswith("same\t"))
+    assert b == a + 1
+    rest[a], rest[b] = rest[b], rest[a]
+    assert rest == stage4 and [x.split("\t")[0] for x in stage4] == ["star", "same", "same", "last"]
+    star = stage4[0].split("\t")
+    assert int(star[1]) == 0x10 and star[9:11] == [M.revcomp("AACCGGTTAC"), "*"] and star[5] == "2S8M"
+    same1 = stage4[2].split("\t")
+    assert same1[4] == "42" and same1[6:9] == ["=", "20", "11"] and same1[10] == "JIHGFEDCBA" and same1[11:] == ["AS:i:20", "XS:i:18", "NM:i:0\n"]
+    assert stage4[1].split("\t")[4] == "0" and stage4[1].split("\t")[8] == "-11"
+
+
 # ---------------------------------------------------------------------------------------------------- command line
 
 def test_command_line_errors_leave_with_2_and_touch_no_device(tmp_path, monkeypatch):
